@@ -17,8 +17,16 @@ stick-figure persons per image, encoder conventions, noise) are ADDED to the hea
 the timed region, so the decoder sees a realistic candidate load and still depends on the
 backbone's result.
 
-Prints ONE JSON line (rank 0) with the driver's keys plus `roofline` (K1, the HBM-bound
-hand-written kernel, timed live with HIP events on the launch stream) and `cpu_baseline`.
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line (rank 0): the driver's keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) plus what the headline region itself measured (`stage_us`, `k1f`,
+`engine`, per-rank HBM, host time per step).  Everything that takes runs of its own is behind `--full`: `roofline` (K1, the
+HBM-bound hand-written kernel, in a second timed region), the decoder-only / backbone-only / C1 / HBM-cold figures, the
+flip-test and other-dtype lines, the `harness` figure and `cpu_baseline`.
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 /
+                       float64, at most DUMP_BUDGET_BYTES in all; see write_outputs): the poses a caller receives and the
+                       engine's raw head outputs (before the synthetic maps are added).  Inputs and weights are seeded: the
+                       same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -43,13 +51,20 @@ FLOP_PER_IMAGE = 732.78e9       # 2 x 366.39 GMAC, convs only, 6
 K1_BYTES_PER_IMAGE = 27_889_280  # 17*640*640*4 read + offset gathers + limbs write
 K1F_BYTES_PER_IMAGE = 5_632_000  # SURVEY.md 8(d), fused production path lower bound: (17 + 38) * 160 * 160 * 4 (x2 with flip-test)
 METRIC = 'images/sec end-to-end (backbone+decode) @640x640 bs8; decoder-only ms/img'
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=30)
+    ap.add_argument('--steps', type=int, default=30, help='timed steps (exactly this many; >= 1)')
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline figure: the roofline region, decoder-only / backbone-only / C1 / '
+                         'HBM-cold figures, flip-test and other-dtype lines, the harness figure and the CPU baseline (the --no-* switches '
+                         'below leave parts of it out)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (poses, head outputs) as DIR/<name>.npy')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--size', type=int, default=640)
     ap.add_argument('--flip', action='store_true', help='flip-test (BASELINE config 3): 2x images through the backbone')
@@ -60,7 +75,7 @@ def parse():
                          'bf16; same MFMA rate, fp16 is 8x closer to the fp32 module')
     ap.add_argument('--no-harness', action='store_true', help='skip the evaluate.run_images figure (raw uint8 host images -> result dicts)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='headline region only: skip the decoder-only / backbone-only / conv / HBM-cold / flip measurements')
+                    help='with --full: skip the decoder-only / backbone-only / conv / HBM-cold / flip / other-dtype / harness measurements')
     ap.add_argument('--allow-diagnostic', action='store_true',
                     help='run although a switch that produces WRONG RESULTS or loads a foreign library is set (OG_ENGINE_WHATIF, OG_BENCH_ZERO_WEIGHTS, '
                          'OG_DECODER_LIB): the JSON line then carries "diagnostic": true and is not a measurement')
@@ -76,7 +91,36 @@ def parse():
     ap.add_argument('--overlap', action='store_true',
                     help='run the decoder on a second HIP stream beside the next backbone (measured: no gain, the\n'
                          'backbone already saturates the chip, and K1 then competes with the convolutions for HBM)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
+
+
+def write_outputs(out_dir, whole, large, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: every array of `whole` is written as it is, those of `large` too while everything fits in `budget` bytes;
+    otherwise each array of `large` is replaced by the same fraction of its elements, taken at fixed flat indices (seeded, sorted:
+    the same shapes give the same sample in every run).  float64 arrays stay float64, everything else is written as float32.
+    -> {name: 'whole' | 'sample of <k> of <n> elements'}"""
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                                      # .npy header bytes per file
+    conv = lambda v: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)   # noqa: E731
+    whole = {k: conv(v) for k, v in whole.items()}
+    large = {k: conv(v) for k, v in large.items()}
+    left = budget - sum(v.nbytes + header for v in whole.values()) - header * len(large)
+    big = sum(v.nbytes for v in large.values())
+    frac = 1.0 if big <= left else max(left, 0) / big
+    done = {}
+    for name, v in list(whole.items()) + list(large.items()):
+        what = 'whole'
+        if name in large and frac < 1.0:
+            flat = v.reshape(-1)
+            k = int(flat.size * frac)
+            v = flat[np.sort(np.random.default_rng(seed).choice(flat.size, size=k, replace=False))]
+            what = f'sample of {k} of {flat.size} elements'
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+        done[name] = what
+    return done
 
 
 def bench_init(model, seed):
@@ -359,6 +403,7 @@ def main():
 
         def features(self, i, engine=None):
             hm_o, off_o = (engine or self.engine).forward_raw(self.images[i % n_rot])
+            self.last_heads = (hm_o, off_o)    # --dump-outputs (graph outputs: valid until that engine's next replay)
             hm, off = hm_o + self.maps[i % n_rot][0], off_o + self.maps[i % n_rot][1]
             return [([None, hm], [[], []], [[], []]), ([None, off], [[], []], [[], []])]
 
@@ -425,6 +470,15 @@ def main():
     engine, proc, maps, images, nb = pipe.engine, pipe.proc, pipe.maps, pipe.images, pipe.nb
     poses, elapsed_rank, elapsed, stage_us = pipe.timed_region(a.steps, a.warmup)
     pipe_host = list(pipe.host_s)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # before anything else runs on the engines: their graph outputs still hold the last timed step's head outputs
+        dumped = write_outputs(a.dump_outputs,
+                               whole={'poses': np.concatenate(poses) if poses else np.zeros((0, 17, 6), np.float32),
+                                      'poses_per_image': np.array([len(x) for x in poses], dtype=np.float64)},
+                               large={'head_heatmaps': pipe.last_heads[0].float().cpu().numpy(),
+                                      'head_offsets': pipe.last_heads[1].float().cpu().numpy()})
+    full_extras = a.full and not a.no_extras
     # every convolution of the forward on a hand-written kernel: the engines are strict (a shape none of them serves raises instead of
     # running on torch / MIOpen); the counter is what a strict=False caller would read
     engine_info = {'strict': all(e.strict for e in pipe.engines), 'torch_conv_calls': sum(len(e.torch_conv_calls) for e in pipe.engines)}
@@ -437,7 +491,7 @@ def main():
     # engine, same inputs, same steps, every rank -- runs a second timed region in its roofline benchmark mode (K1a materialises the
     # hi-res heat maps, K1 streams them) and K1's HIP events of THAT region are what `roofline` reports.
     roof_stage, roof_elapsed = stage_us, None
-    if 'k1_generate_limbs' not in stage_us:
+    if a.full and 'k1_generate_limbs' not in stage_us:
         for pr in pipe.procs:
             pr.fused_upsample = False
         _, _, roof_elapsed, roof_stage = pipe.timed_region(a.steps, a.warmup, serial=True)
@@ -448,7 +502,7 @@ def main():
     # in a serial region of the same pipeline (with two batches in flight the same launches share the CUs with the other batch's
     # convolutions: stage_us of the headline region; DESIGN 4 "The decoder beside the other batch")
     serial_stage = None
-    if not a.no_extras and a.inflight > 1 and 'k1f_fused_limbs' in stage_us:
+    if full_extras and a.inflight > 1 and 'k1f_fused_limbs' in stage_us:
         _, _, _, serial_stage = pipe.timed_region(a.steps, a.warmup, serial=True)
 
     def timed(fn, n):
@@ -466,7 +520,7 @@ def main():
         k1f_1, k3_1 = float(np.mean(serial_stage['k1f_fused_limbs'])), float(np.mean(serial_stage['k3_group']))
         extras['decoder_ms_per_img_inflight1'] = round((k1f_1 + k3_1) * 1e-3 / a.batch, 4)
         extras['decoder_us_per_batch_inflight1'] = {'k1f_fused_limbs': round(k1f_1, 2), 'k3_group': round(k3_1, 2)}
-    if not a.no_extras:
+    if full_extras:
         # ---- decoder-only and backbone-only timings (outside the headline region) ----
         fixed = [[([None, m[0]], [[], []], [[], []]), ([None, m[1]], [[], []], [[], []])] for m in maps]
         was_fused = proc.fused_upsample
@@ -532,7 +586,7 @@ def main():
 
     # ---- BASELINE configs[2] (flip-test) in the same process, same steps: 2x images through the backbone, K0 merge ----
     flip_line = None
-    if not a.no_extras and not a.flip:
+    if full_extras and not a.flip:
         del pipe, engine, proc
         torch.cuda.empty_cache()
         fpipe = Pipeline(True, a.inflight)
@@ -550,7 +604,7 @@ def main():
     # ---- the other 16-bit arithmetic timed in the same process, same steps (headline fp16 = the reference's apex-O2 arithmetic,
     # evaluate.py:92,198-201; the block beside it is the bf16 engine) ----
     alt_line, alt_dtype = None, ('bf16' if a.dtype == 'f16' else 'f16')
-    if not a.no_extras and not a.no_alt_dtype and not a.flip:
+    if full_extras and not a.no_alt_dtype and not a.flip:
         torch.cuda.empty_cache()
         hpipe = Pipeline(False, a.inflight, dtype=alt_dtype)
         _, _, h_elapsed, h_stage = hpipe.timed_region(a.steps, a.warmup)
@@ -566,7 +620,7 @@ def main():
     # ---- the drop-in harness itself: evaluate.run_images fed raw uint8 HWC host images of mixed sizes (pageable memory) --
     # EvalPreprocess (pinned H2D + og_rescale_pad_normalize_u8) -> engine -> PostProcess.submit -> poses_to_results
     harness = None
-    if not a.no_extras and not a.no_harness and not a.flip and rank == 0:
+    if full_extras and not a.no_harness and not a.flip and rank == 0:
         torch.cuda.empty_cache()
         # the figure depends on what else runs on the (shared) host: three passes, the MEDIAN is `value`, all listed, the best one
         # kept as `best` (never quoted as "the" harness rate)
@@ -581,14 +635,31 @@ def main():
     host_us = 1e6 * float(np.mean(pipe_host)) if pipe_host else None
     if rank == 0:
         fused_k1 = False
-        k1 = float(np.mean(roof_stage['k1_generate_limbs']))
         k1_bytes = a.batch * K1_BYTES_PER_IMAGE * (a.size * a.size) / (640 * 640)
-        achieved = k1_bytes / (k1 * 1e-6) / 1e9
-        # HBM bytes per launch from the PMC counters (separate rocprofv3 --pmc passes, profiles/README.md): only a figure
-        # measured on THIS round's kernels is reported
-        k1_kernels = ('band_topk_kernel', 'merge_collect_kernel')
-        traffic, traffic_file = (None, None) if fused_k1 else k1_traffic(k1_kernels)
         imgs = a.batch * a.steps * world
+        roofline = None
+        if 'k1_generate_limbs' in roof_stage:      # the roofline region ran (--full), or the headline decoder itself is K1a + K1
+            k1 = float(np.mean(roof_stage['k1_generate_limbs']))
+            achieved = k1_bytes / (k1 * 1e-6) / 1e9
+            # HBM bytes per launch from the PMC counters (separate rocprofv3 --pmc passes, profiles/README.md): only a figure
+            # measured on THIS round's kernels is reported
+            k1_kernels = ('band_topk_kernel', 'merge_collect_kernel')
+            traffic, traffic_file = (None, None) if fused_k1 else k1_traffic(k1_kernels)
+            roofline = {'kernel': 'K1 at the generate_limbs boundary = og_generate_limbs_f32: band_topk_kernel + '
+                                  'merge_collect_kernel' + ('' if roof_elapsed is None else
+                                  ', HIP events inside a second timed region of the same pipeline in its roofline benchmark mode '
+                                  '(fused_upsample=False: K1a + K1, one batch at a time); the headline region runs the production decoder K1-fused '
+                                  '(stage_us.k1f_fused_limbs), which never builds the hi-res tensor'),
+                        'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': round(achieved / HBM_PEAK_GBS, 4),
+                        # against what a float4 copy reaches on this chip (6.29 TB/s, MI355X_MICROARCH.md "HBM"): the stream
+                        # kernel alone runs at ~0.85 of that; the generate_limbs boundary adds the merge / pairing launch
+                        'frac_of_achievable': round(achieved / HBM_ACHIEVABLE_GBS, 4),
+                        'traffic': traffic, 'traffic_source': traffic_file,
+                        'us_per_launch': round(k1, 2), 'algorithmic_bytes_per_launch': int(k1_bytes),
+                        **({} if roof_elapsed is None else
+                           {'region': {'images_per_sec': round(imgs / roof_elapsed, 2), 'ms_per_step': round(roof_elapsed / a.steps * 1e3, 3),
+                                       'stage_us': {k: round(float(np.mean(v)), 2) for k, v in roof_stage.items()}}})}
         line = {
             'metric': METRIC,
             'value': round(imgs / elapsed, 2), 'unit': 'images/sec', 'n_gpus': world, 'steps': a.steps,
@@ -605,21 +676,7 @@ def main():
             'per_rank_hbm_bytes': per_rank_hbm,
             'poses_last_batch': [int(len(x)) for x in poses],
             'stage_us': {k: round(float(np.mean(v)), 2) for k, v in stage_us.items()},
-            'roofline': {'kernel': 'K1 at the generate_limbs boundary = og_generate_limbs_f32: band_topk_kernel + '
-                                   'merge_collect_kernel' + ('' if roof_elapsed is None else
-                                   ', HIP events inside a second timed region of the same pipeline in its roofline benchmark mode '
-                                   '(fused_upsample=False: K1a + K1, one batch at a time); the headline region runs the production decoder K1-fused '
-                                   '(stage_us.k1f_fused_limbs), which never builds the hi-res tensor'),
-                         'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(achieved / HBM_PEAK_GBS, 4),
-                         # against what a float4 copy reaches on this chip (6.29 TB/s, MI355X_MICROARCH.md "HBM"): the stream
-                         # kernel alone runs at ~0.85 of that; the generate_limbs boundary adds the merge / pairing launch
-                         'frac_of_achievable': round(achieved / HBM_ACHIEVABLE_GBS, 4),
-                         'traffic': traffic, 'traffic_source': traffic_file,
-                         'us_per_launch': round(k1, 2), 'algorithmic_bytes_per_launch': int(k1_bytes),
-                         **({} if roof_elapsed is None else
-                            {'region': {'images_per_sec': round(imgs / roof_elapsed, 2), 'ms_per_step': round(roof_elapsed / a.steps * 1e3, 3),
-                                        'stage_us': {k: round(float(np.mean(v)), 2) for k, v in roof_stage.items()}}})},
+            **({'roofline': roofline} if roofline is not None else {}),
             **({'k1f': {'kernel': 'K1-fused (production) = og_generate_limbs_fused_f32: band_topk_kernel<fused> (x4 bicubic + NMS + top-k from '
                                   'the stride-4 maps) + merge_collect_kernel<fused>; instruction-issue bound (valu_issue_frac from the PMC passes), no HBM roofline claim (SURVEY 8d)',
                         'us_per_launch': round(float(np.mean(stage_us['k1f_fused_limbs'])), 2),
@@ -648,8 +705,10 @@ def main():
             line['flip'] = flip_line
         if alt_line is not None:
             line[alt_dtype] = alt_line
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(a, model, maps, cd)
+        if dumped is not None:
+            line['dumped_outputs'] = dumped
         print(json.dumps(line))
     import torch.distributed as dist
     if dist.is_initialized():

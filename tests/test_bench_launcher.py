@@ -193,3 +193,74 @@ def test_two_rank_bench_on_the_gpu():
     hbm = line['per_rank_hbm_bytes']
     assert len(hbm) == 2 and all(1 << 30 < b < 64 << 30 for b in hbm), hbm      # weights + two engines' activations: a few GB of the 288
     assert line['host_us_per_step'] > 0 and line['knobs']['GPU_MAX_HW_QUEUES'] == '4'
+
+
+def test_plain_run_flags_and_step_count_are_checked():
+    """--full and --dump-outputs are accepted (control plane only here); --steps sets the number of timed steps and must be >= 1."""
+    r = subprocess.run([sys.executable, BENCH, '--steps', '4', '--warmup', '0', '--full', '--dump-outputs', 'unused', '--dry-run'],
+                       capture_output=True, text=True, timeout=120, env=_clean_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_line(r.stdout)
+    assert line['steps'] == 4 and line['warmup'] == 0 and 'ms_per_step' in line
+    r = subprocess.run([sys.executable, BENCH, '--steps', '0', '--dry-run'], capture_output=True, text=True, timeout=120,
+                       env=_clean_env())
+    assert r.returncode != 0 and '--steps must be >= 1' in r.stderr
+
+
+def test_write_outputs_keeps_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: small arrays are written whole, large ones whole while all fits in the budget, otherwise as the same seeded
+    sample in every run; every file is float32 or float64."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod3', BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000
+    rng = np.random.default_rng(5)
+    whole = {'poses': rng.standard_normal((7, 17, 6)).astype(np.float32), 'counts': np.array([3, 4], dtype=np.float64)}
+    large = {'hm': rng.standard_normal((2, 17, 40, 40)).astype(np.float32), 'off': rng.standard_normal((2, 38, 40, 40)).astype(np.float16)}
+    done = bench.write_outputs(str(tmp_path / 'all'), whole, large)
+    assert set(done.values()) == {'whole'}
+    for name, v in {**whole, **large}.items():
+        got = np.load(tmp_path / 'all' / f'{name}.npy')
+        assert got.dtype in (np.float32, np.float64) and got.shape == v.shape and np.array_equal(got, v.astype(got.dtype))
+    budget = 60_000
+    runs = [bench.write_outputs(str(tmp_path / f's{i}'), whole, large, budget=budget) for i in range(2)]
+    assert runs[0] == runs[1] and runs[0]['poses'] == 'whole' and runs[0]['hm'].startswith('sample of ')
+    for d in ('s0', 's1'):
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget
+    for name in large:
+        a, b = np.load(tmp_path / 's0' / f'{name}.npy'), np.load(tmp_path / 's1' / f'{name}.npy')
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < large[name].size and np.array_equal(a, b)
+        assert np.isin(a, large[name].astype(np.float32).ravel()).all()       # elements of the output, not something else
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run times exactly --steps steps, carries the headline keys and nothing that takes a run of its own, and
+    --dump-outputs writes the last step's poses and head outputs: float32 / float64, under 64 MB, the same in two runs."""
+    import numpy as np
+    lines = []
+    for d in ('a', 'b'):
+        r = subprocess.run([sys.executable, BENCH, '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=900, env=_clean_env())
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines.append(_json_line(r.stdout))
+    line = lines[0]
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['unit'] == 'images/sec' and line['higher_is_better'] is True
+    assert line['dtype'] == 'f16' and line['metric'] and line['value'] > 0 and line['ms_per_step'] > 0
+    assert abs(line['value'] - 8 * 3 / (line['ms_per_step'] * 3e-3)) / line['value'] < 1e-3
+    assert not {'cpu_baseline', 'flip', 'bf16', 'harness', 'roofline', 'backbone_ms_per_batch'} & set(line)
+    assert line['engine'] == {'strict': True, 'torch_conv_calls': 0}
+    names = {'poses', 'poses_per_image', 'head_heatmaps', 'head_offsets'}
+    assert set(line['dumped_outputs']) == names
+    assert sorted(os.listdir(tmp_path / 'a')) == sorted(n + '.npy' for n in names)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) <= 64_000_000
+    out = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out['poses_per_image'].tolist() == line['poses_last_batch'] and len(out['poses']) == sum(line['poses_last_batch'])
+    assert out['head_heatmaps'].shape == (8, 17, 160, 160) and out['head_offsets'].shape == (8, 38, 160, 160)
+    assert np.isfinite(out['head_heatmaps']).all() and sum(line['poses_last_batch']) > 0
+    for n in names:       # seeded inputs and weights, deterministic kernels: the same arguments give the same outputs
+        assert np.array_equal(out[n], np.load(tmp_path / 'b' / f'{n}.npy')), n

@@ -40,11 +40,31 @@ def _load_inputs():
     return hm_pred, hm_gt, off_pred, off_gt, ps, mask
 
 
+class IeeeSqrt(torch.autograd.Function):
+    """torch.sqrt with a correctly rounded forward (numpy's: the processor's sqrt instruction) and torch's own backward,
+    grad / (2 * result).  torch.sqrt on the CPU is MKL's vector sqrt, which is not correctly rounded and takes a different code
+    path, with different last bits, on each processor family (Intel AVX-512, Intel AVX2, AMD ...), whatever MKL_CBWR says.  The
+    golden cases with sqrt_re compute sqrt with this on both sides -- the reference's and ours (tools/gen_golden_losses.py) --
+    so that they hold bit for bit on any CPU."""
+
+    @staticmethod
+    def forward(ctx, x):
+        r = torch.from_numpy(np.sqrt(x.detach().numpy()))
+        ctx.save_for_backward(r)
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        (r,) = ctx.saved_tensors
+        return g / (2 * r)
+
+
 @pytest.mark.parametrize("sqrt_re", [False, True])
 @pytest.mark.parametrize("off_name", ["offset_l1_loss", "offset_instance_l1_loss"])
-def test_losses_match_reference_golden(sqrt_re, off_name):
+def test_losses_match_reference_golden(sqrt_re, off_name, monkeypatch):
     g = np.load(f"{GOLDEN}/losses.npz")
     tag = f"{off_name}_{int(sqrt_re)}"
+    monkeypatch.setattr(torch, "sqrt", IeeeSqrt.apply)      # as the fixture was computed: see IeeeSqrt
     hm, off, ghm, goff = _run(losses, _load_inputs(), sqrt_re, off_name)
     assert np.float32(hm) == g[tag + "_hm"] and np.float32(off) == g[tag + "_off"]
     assert np.array_equal(np.stack(ghm)[:, :, :3, ::4, ::4], g[tag + "_ghm"])

@@ -16,13 +16,19 @@ import oracle  # noqa: E402
 from offsetguided_amd import synth  # noqa: E402
 from offsetguided_amd.config.coco_data import COCO_PERSON_SIGMAS, COCO_PERSON_SKELETON  # noqa: E402
 
-sys.modules.setdefault('cv2', types.ModuleType('cv2'))
-sys.path.insert(0, '/root/reference')
-from encoder.heatmap import HeatMapGenerator  # noqa: E402
-from encoder.offset import OffsetMapGenerator  # noqa: E402
-sys.path.remove('/root/reference')
-
 GOLD = os.path.join(ROOT, 'tests', 'golden')
+
+
+def load_reference_generators():
+    """The reference's HeatMapGenerator / OffsetMapGenerator from its checkout (gen_golden.REF, OG_REFERENCE), imported when the
+    fixture is generated: importing this tool needs nothing outside the repository."""
+    from tools.gen_golden import REF
+    sys.modules.setdefault('cv2', types.ModuleType('cv2'))
+    sys.path.insert(0, REF)
+    from encoder.heatmap import HeatMapGenerator
+    from encoder.offset import OffsetMapGenerator
+    sys.path.remove(REF)
+    return HeatMapGenerator, OffsetMapGenerator
 
 
 def random_joints(seed, persons, size):
@@ -42,6 +48,7 @@ def random_joints(seed, persons, size):
 
 
 def main():
+    HeatMapGenerator, OffsetMapGenerator = load_reference_generators()
     out = {}
     for name, seed, persons, size in (('a', 11, 6, 256), ('b', 12, 30, 256), ('c', 13, 0, 128), ('d', 14, 12, 512)):
         j = random_joints(seed, persons, size)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Golden values for the training losses from the imported reference models/losses.py (build
-container only).  Inputs come from the portable generator; expected values/gradients are stored."""
+container only).  Inputs come from the portable generator; expected values/gradients are stored.  torch.sqrt is
+tests/test_losses.py:IeeeSqrt on both sides (correctly rounded: MKL's CPU sqrt differs in the last bit between processors)."""
 import importlib.util
 import os
 import sys
@@ -14,9 +15,15 @@ sys.dont_write_bytecode = True
 from offsetguided_amd import synth  # noqa: E402
 from offsetguided_amd.models import losses as mine  # noqa: E402
 
-spec = importlib.util.spec_from_file_location('ref_losses', '/root/reference/models/losses.py')
-ref = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(ref)
+
+def load_reference_losses():
+    """The reference's models/losses.py from its checkout (gen_golden.REF, OG_REFERENCE), loaded when the fixture is generated:
+    importing this tool needs nothing outside the repository."""
+    from tools.gen_golden import REF
+    spec = importlib.util.spec_from_file_location('ref_losses', os.path.join(REF, 'models', 'losses.py'))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    return ref
 
 
 def inputs(seed=5, n=2, h=32, w=32):
@@ -45,6 +52,10 @@ def run(mod, hm_pred, hm_gt, off_pred, off_gt, ps, mask, sqrt_re, off_name):
 
 
 def main():
+    ref = load_reference_losses()
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from test_losses import IeeeSqrt
+    torch.sqrt = IeeeSqrt.apply          # the reference and ours alike
     out = {}
     inp = inputs()
     for sqrt_re in (False, True):

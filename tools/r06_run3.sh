@@ -9,6 +9,6 @@ timeout 1200 python -m pytest tests -m gpu -x -q -k "batched_input_chain or fold
 tail -15 "$out/pytest_new.log"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1
 tail -3 "$out/smoke.log"
-timeout 900 python bench.py > "$out/bench.json" 2> "$out/bench.err"
+timeout 900 python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 tail -c 6000 "$out/bench.json"
 tail -5 "$out/bench.err"
