@@ -209,6 +209,19 @@ int og_flip_cat_f32(const float *hm, const float *off, int N, int C, int L, int 
                     const int32_t *kp_perm, const int32_t *limb_perm, const int32_t *reserve_mask,
                     float *hm_out, float *off_out, void *stream);
 
+/* ---- multi-scale test: one scale's head outputs onto the base grid  (decoder/multiscale.py; beyond the reference) ----
+ * hm (F*N,C,hs,ws), off (F*N,2L,hs,ws) of the scale, F = 2 with flip (the [images | mirrored images] pair, merged as
+ * og_flip_merge_f32 merges it: kp_perm / limb_perm / reserve_mask as there, may be NULL without flip), F = 1 without.
+ * aff (N,6) fp32 device table per image: Ax, Bx, Ay, By, inv_ax, inv_ay.  Base cell (j, i): u = Ax*j + Bx clamped to
+ * [0, ws-1], x0 = floor(u), x1 = min(x0+1, ws-1), fx = u - x0 (rows alike); top = p00*(1-fx) + p01*fx, bot = p10*(1-fx) +
+ * p11*fx, v = top*(1-fy) + bot*fy; offsets then v*inv_ax (x, even channels) / v*inv_ay (y, odd channels).
+ * hm_acc (N,C,h,w), off_acc (N,2L,h,w): mode 0 writes v, 1 adds v, 2 adds v then multiplies by inv_count (the last scale).
+ * The identity table (1, 0, 1, 0, 1, 1) reproduces the (merged) input.  One launch for both maps. */
+int og_scale_accumulate_f32(const float *hm, const float *off, int N, int flip, int C, int L, int hs, int ws,
+                            const int32_t *kp_perm, const int32_t *limb_perm, const int32_t *reserve_mask,
+                            const float *aff, int h, int w, int mode, float inv_count, float *hm_acc, float *off_acc,
+                            void *stream);
+
 /* ---- backbone epilogues (bf16, channels-last / NHWC activations of the inference engine) ----
  * Stand-alone epilogue / layout passes.  In the engine every convolution carries its epilogue itself (og_conv*_ below);
  * og_bias_act_* is what remains for a convolution that torch ran (InferenceEngine(strict=False) only), og_upsample2_add_* the

@@ -46,6 +46,7 @@ SIGNATURES = {
     "og_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "og_flip_merge_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_flip_cat_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_scale_accumulate_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "og_bias_act_bf16": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
     "og_upsample2_add_bf16": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
     "og_nchw_f32_to_nhwc_bf16": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
@@ -116,6 +117,10 @@ def load():
             raise ImportError(f"{LIB_PATH}: ABI version {lib.og_abi_version()} != {ABI_VERSION}; rebuild with "
                               "`python -m offsetguided_amd.build --force`")
         for name, (res, args) in SIGNATURES.items():
+            # entry points added without a version change (og_scale_accumulate_f32: the ABI only grew) -- a library built before
+            # them says so here instead of with a bare AttributeError
+            if not hasattr(lib, name):
+                raise ImportError(f"{LIB_PATH} lacks {name}: stale build; rebuild with `python -m offsetguided_amd.build --force`")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

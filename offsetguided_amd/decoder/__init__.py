@@ -5,3 +5,4 @@ from .offset import scored_offset  # noqa: F401
 from .group import GreedyGroup, soft_nms  # noqa: F401
 from .collect import LimbsCollect  # noqa: F401
 from .factory import decoder_factory, decoder_cli, PostProcess  # noqa: F401
+from .multiscale import merge_scales, scale_affines  # noqa: F401  (multi-scale test: beyond the reference)

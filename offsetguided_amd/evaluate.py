@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, decoder, models
+from .decoder import multiscale
 from .utils import AverageMeter
 
 LOG = logging.getLogger(__name__)
@@ -45,6 +46,9 @@ def evaluate_cli(argv=None):
     parser.add_argument('--fixed-height', action='store_true', default=False)
     parser.add_argument('--flip-test', action='store_true', default=False, help='flip augmentation during testing')
     parser.add_argument('--cat-flip-offset', action='store_true', default=False)
+    parser.add_argument('--test-scales', default=[1.0], type=float, nargs='+', metavar='S',
+                        help='multi-scale test (beyond the reference): input scales relative to --long-edge whose head outputs are '
+                             'averaged on the grid of scale 1 (which must be in the list) and decoded once')
     parser.add_argument('--loader-workers', default=8, type=int)
     parser.add_argument('--all-images', default=False, action='store_true')
     parser.add_argument('--resume', '-r', action='store_true', default=False, help='load --checkpoint-whole')
@@ -58,12 +62,35 @@ def evaluate_cli(argv=None):
     g.add_argument('--channels-last', default=False, action='store_true')
     g.add_argument('--print-freq', '-f', default=10, type=int, metavar='N')
     args = parser.parse_args(argv)
+    try:
+        validate_test_scales(args.test_scales, args.fixed_height, args.cat_flip_offset)
+    except ValueError as e:
+        parser.error(str(e))
     args.image_dir, args.annotation_file = {
         'val': (IMAGE_DIR_VAL, ANNOTATIONS_VAL), 'test': (IMAGE_DIR_TEST, ANNOTATIONS_TEST),
         'test-dev': (IMAGE_DIR_TEST, ANNOTATIONS_TESTDEV)}[args.dataset]
     if args.dataset in ('test', 'test-dev'):
         args.all_images = True
     return args
+
+
+def validate_test_scales(scales, fixed_height=False, cat_flip_offset=False):
+    """--test-scales: positive, no repeats, 1.0 present (its grid and metas are the ones decoded and mapped back); more than one scale
+    is not served with --fixed-height or --cat-flip-offset (decoder/multiscale.py).  Raises ValueError."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError('--test-scales: at least one scale')
+    if any(not s > 0 for s in scales):
+        raise ValueError(f'--test-scales: every scale must be > 0, got {scales}')
+    if len(set(scales)) != len(scales):
+        raise ValueError(f'--test-scales: duplicate scales in {scales}')
+    if 1.0 not in scales:
+        raise ValueError(f'--test-scales: 1.0 must be one of the scales (the base grid), got {scales}')
+    if len(scales) > 1 and fixed_height:
+        raise ValueError('--test-scales with more than one scale is not implemented with --fixed-height')
+    if len(scales) > 1 and cat_flip_offset:
+        raise ValueError('--test-scales with more than one scale is not implemented with --cat-flip-offset')
+    return scales
 
 
 def annotations_inverse(keypoints, meta):
@@ -131,7 +158,9 @@ IN_FLIGHT = 2
 def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=None):
     """The hot loop of evaluate.py:207-298.  Returns (result_keypoints, result_image_ids).
     stats: an optional dict that receives `host_enqueue_s` (per batch: host time to queue the input chain, the forward and the decoder --
-    no wait in it), `engines_built` and `torch_conv_calls` (0: every engine is strict, models/engine.py)."""
+    no wait in it), `engines_built`, `torch_conv_calls` (0: every engine is strict, models/engine.py), `test_scales` and
+    `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it).
+    args.test_scales (--test-scales, default [1.0]): more than one scale runs the multi-scale test (enqueue_multi_scale below)."""
     if not torch.cuda.is_available():
         raise RuntimeError('run_images needs a HIP device (offsetguided_amd has no CPU path)')
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -192,49 +221,127 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 nxt = None
             yield cur
 
+    def engine_slot(shape, batch_idx):
+        """[engine, index of the last batch it ran, event behind that batch] for an input shape (built or reused, see above)."""
+        of_shape = engines.pop(shape, None)
+        if of_shape is None:
+            if len(engines) >= ENGINE_CACHE:
+                while pending:               # the batches in flight still read the outputs of the engines that go
+                    collect(pending.popleft())
+                engines.popitem(last=False)
+            of_shape = []
+        engines[shape] = of_shape          # most recently used last
+        slot = min(of_shape, key=lambda e: e[1], default=None)           # the engine of this shape that has rested longest
+        if slot is None or (batch_idx - slot[1] < len(lanes) and len(of_shape) < len(lanes)):
+            slot = [models.InferenceEngine(model, shape[0], shape[2], shape[3], device=dev,
+                                           feat_stage=args.feat_stage, like=first_engine[0]), -len(lanes), None]
+            first_engine[0] = first_engine[0] or slot[0]      # the module's weights do not change inside one call
+            of_shape.append(slot)
+            if stats is not None:
+                stats['engines_built'] = stats.get('engines_built', 0) + 1
+                stats.setdefault('_engines', []).append(slot[0])
+        return slot
+
+    # multi-scale test (--test-scales with more than one scale; decoder/multiscale.py): per batch and scale the input chain
+    # (EvalPreprocess.multi_scale: one H2D copy, one launch per scale), the engine of that scale's shape, then one og_scale_accumulate_f32
+    # launch per scale into the lane's base-grid accumulators and one submit of the averaged maps.  [1.0] runs the code above unchanged.
+    scales = validate_test_scales(getattr(args, 'test_scales', [1.0]), getattr(args, 'fixed_height', False),
+                                  getattr(args, 'cat_flip_offset', False))
+    multi = len(scales) > 1
+    if multi and len(scales) > ENGINE_CACHE:
+        raise ValueError(f'--test-scales: at most {ENGINE_CACHE} scales (the engines of one batch must all stay cached)')
+    base = scales.index(1.0)
+    accumulators = [None] * len(lanes)
+
+    def enqueue_multi_scale(batch_idx, images, metas, packed):
+        nonlocal full_batch
+        if packed is None:
+            raise ValueError('--test-scales with more than one scale needs batches of raw (h, w, 3) uint8 images: a tensor batch '
+                             'cannot be rescaled')
+        per_scale = preprocess[0].multi_scale(images, scales, image_ids=[m['image_id'] for m in metas], packed=packed.result())
+        base_metas = per_scale[base][1]
+        n = len(base_metas)
+        full_batch = full_batch or n
+        lane = batch_idx % len(lanes)
+        cur = torch.cuda.current_stream(dev)
+        inputs, tables = [], []
+        base_hw = tuple(s_ // 4 for s_ in per_scale[base][0].shape[2:])
+        for x, metas_s in per_scale:
+            aff = decoder.scale_affines(base_metas, metas_s, base_hw, tuple(s_ // 4 for s_ in x.shape[2:]))
+            if n < full_batch:         # last batch of the dataset: filled up to the engine's batch, results are dropped
+                x = torch.cat((x, x[-1:].expand(full_batch - n, -1, -1, -1)))
+                aff = np.concatenate((aff, np.repeat(aff[-1:], full_batch - n, axis=0)))
+            if args.flip_test:
+                x = torch.cat((x, torch.flip(x, [-1])))
+            inputs.append(x)
+            tables.append(aff)
+        aff_dev = torch.from_numpy(np.stack(tables)).pin_memory().to(dev, non_blocking=True)
+        slots = []
+        for x in inputs:
+            slot = engine_slot(tuple(x.shape), batch_idx)
+            slot[1] = batch_idx          # taken: a second scale of the same padded size gets another engine, or runs after this one
+            slots.append(slot)
+        if lanes[lane] is not cur:
+            lanes[lane].wait_stream(cur)                 # the input chain, the flips and the affine tables ran / were copied on `cur`
+            for x in inputs:
+                x.record_stream(lanes[lane])
+            aff_dev.record_stream(lanes[lane])
+        proc = processors[lane]
+        inv = float(np.float32(1.0) / np.float32(len(scales)))
+        with torch.cuda.stream(lanes[lane]):
+            if accumulators[lane] is None or tuple(accumulators[lane][0].shape[2:]) != base_hw:
+                accumulators[lane] = (torch.empty((full_batch, len(proc.keypoints)) + base_hw, dtype=torch.float32, device=dev),
+                                      torch.empty((full_batch, 2 * len(proc.skeleton)) + base_hw, dtype=torch.float32, device=dev))
+            for slot in slots:
+                if slot[2] is not None:
+                    lanes[lane].wait_event(slot[2])      # the engine's last batch (maybe on another lane): its merge has read the outputs
+            for s, (x, slot) in enumerate(zip(inputs, slots)):
+                # scale by scale: forward, then its merge, then the engine's event -- two scales of one padded size may share an engine,
+                # whose graph outputs the second forward overwrites (stream order: after the first merge has read them)
+                hm, off, *rest = slot[0].forward_raw(x)
+                if rest:
+                    raise NotImplementedError('multi-scale test merges the heatmap and offset heads only (no keypoint-scale / jitter head)')
+                mode = multiscale.MODE_WRITE if s == 0 else (multiscale.MODE_ADD_SCALE if s == len(inputs) - 1 else multiscale.MODE_ADD)
+                multiscale.accumulate_scale(hm, off, aff_dev[s], accumulators[lane], mode, inv, args.flip_test, proc.keypoints,
+                                            proc.skeleton)
+                slot[2] = torch.cuda.Event()
+                slot[2].record(lanes[lane])
+            # the accumulators are read by K1 on this lane before the lane's next batch writes them (stream order)
+            empty = [[] for _ in range(slot[0].n_stacks)]
+            feats = [([accumulators[lane][0]] * len(empty), list(empty), list(empty)),
+                     ([accumulators[lane][1]] * len(empty), list(empty), list(empty))]
+            return (proc.submit(feats, flip_test=False), base_metas)
+
     try:
         for batch_idx, ((images, _, metas), packed) in enumerate(ahead(data_loader)):
             t_host = time.perf_counter()
-            if packed is not None:
-                # raw (h, w, 3) uint8 RGB images of any size: the input chain of evaluate.py:157-168 runs on the device
-                # (RescaleLongAbsolute + CenterPad, or with --fixed-height RescaleHighAbsolute + RightDownPad of :150-156, then
-                # ToTensor + Normalize; pinned staging packed a batch ahead, one H2D copy); metas are derived here
-                images, metas = preprocess[0](images, image_ids=[m['image_id'] for m in metas], packed=packed.result())
-            images = feeder(images)
-            full_batch = full_batch or images.shape[0]
-            if images.shape[0] < full_batch:   # last batch of the dataset: fill up to the engine's batch, results are dropped
-                images = torch.cat((images, images[-1:].expand(full_batch - images.shape[0], -1, -1, -1)))
-            if args.flip_test:
-                images = torch.cat((images, torch.flip(images, [-1])))
-            lane = batch_idx % len(lanes)
-            of_shape = engines.pop(tuple(images.shape), None)
-            if of_shape is None:
-                if len(engines) >= ENGINE_CACHE:
-                    while pending:               # the batches in flight still read the outputs of the engines that go
-                        collect(pending.popleft())
-                    engines.popitem(last=False)
-                of_shape = []
-            engines[tuple(images.shape)] = of_shape          # most recently used last
-            slot = min(of_shape, key=lambda e: e[1], default=None)           # the engine of this shape that has rested longest
-            if slot is None or (batch_idx - slot[1] < len(lanes) and len(of_shape) < len(lanes)):
-                slot = [models.InferenceEngine(model, images.shape[0], images.shape[2], images.shape[3], device=dev,
-                                               feat_stage=args.feat_stage, like=first_engine[0]), -len(lanes), None]
-                first_engine[0] = first_engine[0] or slot[0]      # the module's weights do not change inside one call
-                of_shape.append(slot)
-                if stats is not None:
-                    stats['engines_built'] = stats.get('engines_built', 0) + 1
-                    stats.setdefault('_engines', []).append(slot[0])
-            cur = torch.cuda.current_stream(dev)
-            if lanes[lane] is not cur:
-                lanes[lane].wait_stream(cur)                 # the input chain (H2D copy, rescale / pad / normalize, flip) ran on `cur`
-                images.record_stream(lanes[lane])
-            if slot[2] is not None:
-                lanes[lane].wait_event(slot[2])              # the engine's last batch (maybe on another lane): its decoder has read the outputs
-            with torch.cuda.stream(lanes[lane]):
-                outputs = slot[0](images)
-                handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset), metas)
-                slot[1], slot[2] = batch_idx, torch.cuda.Event()
-                slot[2].record(lanes[lane])
+            if multi:
+                handle = enqueue_multi_scale(batch_idx, images, metas, packed)
+            else:
+                if packed is not None:
+                    # raw (h, w, 3) uint8 RGB images of any size: the input chain of evaluate.py:157-168 runs on the device
+                    # (RescaleLongAbsolute + CenterPad, or with --fixed-height RescaleHighAbsolute + RightDownPad of :150-156, then
+                    # ToTensor + Normalize; pinned staging packed a batch ahead, one H2D copy); metas are derived here
+                    images, metas = preprocess[0](images, image_ids=[m['image_id'] for m in metas], packed=packed.result())
+                images = feeder(images)
+                full_batch = full_batch or images.shape[0]
+                if images.shape[0] < full_batch:   # last batch of the dataset: fill up to the engine's batch, results are dropped
+                    images = torch.cat((images, images[-1:].expand(full_batch - images.shape[0], -1, -1, -1)))
+                if args.flip_test:
+                    images = torch.cat((images, torch.flip(images, [-1])))
+                lane = batch_idx % len(lanes)
+                slot = engine_slot(tuple(images.shape), batch_idx)
+                cur = torch.cuda.current_stream(dev)
+                if lanes[lane] is not cur:
+                    lanes[lane].wait_stream(cur)                 # the input chain (H2D copy, rescale / pad / normalize, flip) ran on `cur`
+                    images.record_stream(lanes[lane])
+                if slot[2] is not None:
+                    lanes[lane].wait_event(slot[2])              # the engine's last batch (maybe on another lane): its decoder has read the outputs
+                with torch.cuda.stream(lanes[lane]):
+                    outputs = slot[0](images)
+                    handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset), metas)
+                    slot[1], slot[2] = batch_idx, torch.cuda.Event()
+                    slot[2].record(lanes[lane])
             pending.append(handle)
             if stats is not None:
                 stats.setdefault('host_enqueue_s', []).append(time.perf_counter() - t_host)
@@ -259,6 +366,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
             packer[0].shutdown(wait=True, cancel_futures=True)
         if stats is not None:
             stats['torch_conv_calls'] = sum(len(e.torch_conv_calls) for e in stats.pop('_engines', []))
+            stats['test_scales'] = list(scales)
+            stats['engines_per_shape'] = {'x'.join(str(v) for v in shape): len(of) for shape, of in engines.items()}
     return result_keypoints, result_image_ids
 
 

@@ -6,4 +6,4 @@ algorithm; pinned to the CPU restatement in oracle/, parity with cv2 itself unpi
 kernel per image writing straight into the fp32 batch tensor, host images staged through pinned double buffers; plus the
 meta bookkeeping `annotations_inverse` needs."""
 from .pad import CenterPadNormalize, center_pad_ltrb  # noqa: F401
-from .scale import EvalPreprocess, initial_meta, rescale_meta, rescale_size, resize_cubic  # noqa: F401
+from .scale import EvalPreprocess, initial_meta, multi_scale_sizes, rescale_meta, rescale_size, resize_cubic  # noqa: F401

@@ -164,3 +164,55 @@ class EvalPreprocess:
         cur.wait_stream(self.copy_stream)
         out.record_stream(cur)
         return out, metas
+
+    def multi_scale(self, images, scales, image_ids=None, packed=None):
+        """The input chain at several scales (multi-scale test, decoder/multiscale.py) -> [(tensor_s, metas_s) per scale].  ONE H2D copy
+        of the packed batch, then one og_rescale_pad_normalize_batch_u8 launch per scale, all on the copy stream.  Scale s:
+        RescaleLongAbsolute(T_s) + CenterPad(P_s) with T_s = floor(long_edge*s + 0.5) and P_s = T_s rounded up to a multiple of
+        max_stride (multi_scale_sizes); the kernel centre-pads both axes when the rescaled image is smaller than P_s."""
+        if self.fixed_height:
+            raise NotImplementedError('multi-scale test with --fixed-height (RightDownPad) is not implemented')
+        lib = _lib.load()
+        stage, sizes, total = packed if packed is not None else self.pack(images)
+        assert len(sizes) == len(images)
+        n = len(sizes)
+        res = []
+        with torch.cuda.stream(self.copy_stream):
+            dev_raw = torch.empty(total, dtype=torch.uint8, device=self.device)
+            dev_raw.copy_(stage[0][:total], non_blocking=True)
+            stage[1] = torch.cuda.Event()
+            stage[1].record(self.copy_stream)
+            offs, o = (C.c_long * n)(), 0
+            for i, (h, w) in enumerate(sizes):
+                offs[i] = o
+                o += h * w * 3
+            for s in scales:
+                T, P = multi_scale_sizes(self.long_edge, s, self.max_stride)
+                targets = [rescale_size(w, h, T) for h, w in sizes]
+                out = torch.empty((n, 3, P, P), dtype=torch.float32, device=self.device)
+                hw4, ltrb = (C.c_int * (4 * n))(), (C.c_int * (4 * n))()
+                for i, (h, w) in enumerate(sizes):
+                    hw4[4 * i:4 * i + 4] = [h, w, targets[i][1], targets[i][0]]
+                _lib.check(lib.og_rescale_pad_normalize_batch_u8(_lib.ptr(dev_raw), offs, hw4, n, P, P, 0, self._mean, self._std,
+                                                                 self._fill, _lib.ptr(out), ltrb, _lib.stream_ptr(self.device)), lib)
+                metas = []
+                for i, (h, w) in enumerate(sizes):
+                    tw, th = targets[i]
+                    meta, _ = rescale_meta(initial_meta(w, h, None if image_ids is None else image_ids[i]), None, w, h, tw, th)
+                    meta['offset'] = meta['offset'] - np.array(ltrb[4 * i:4 * i + 2], np.float64)          # CenterPad
+                    meta['valid_area'][:2] += np.array(ltrb[4 * i:4 * i + 2], np.float64)
+                    meta['width_height'] = np.array([P, P])
+                    metas.append(meta)
+                res.append((out, metas))
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(self.copy_stream)
+        for out, _ in res:
+            out.record_stream(cur)
+        return res
+
+
+def multi_scale_sizes(long_edge, scale, max_stride=128):
+    """(T_s, P_s) of the multi-scale input chain: the rescaled long edge floor(long_edge*s + 0.5) and the square it is centre-padded
+    to, the next multiple of max_stride (the engine's input constraint)."""
+    T = int(math.floor(long_edge * scale + 0.5))
+    return T, max_stride * -(-T // max_stride)
