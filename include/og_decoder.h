@@ -179,6 +179,33 @@ int og_generate_limbs_fused_flip_f32(const float *hm_pair_lr, const int32_t *kp_
                                      float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace,
                                      size_t workspace_bytes, void *stream);
 
+/* ---- a13: scored_offset  decoder/offset.py:8-43 (PostProcess: kernel_size 3, decoder/factory.py:70-72) ----
+ * Heatmap-weighted offset refinement on the stride-4 maps: hm (N,C,h,w), off / out (N,2L,h,w) contiguous fp32, out must not alias off;
+ * jf int32[L] device array, the start joint of every limb (pack_jtypes, 0-based).  Per limb l and component c
+ *   out[n,2l+c] = box(hm[n,jf[l]] * off[n,2l+c]) / (box(hm[n,jf[l]]) + 1e-6f),
+ * box = the sum over the ksize x ksize window clipped to the plane, with the rounding of the torch-CPU formulation: products rounded
+ * before any sum (no FMA), both sums from +0 over the in-bounds cells row-major, one after the other; a correctly rounded divide.
+ * Bit-identical to decoder.offset.scored_offset on CPU tensors.  ksize odd, 1..7 (anything else: OG_EINVAL).  One streaming launch
+ * (LDS-tiled row bands, 16-byte accesses when w % 4 == 0 and the pointers are 16-byte aligned, a scalar path otherwise); no
+ * allocation, no synchronisation, graph-capturable.  jf[l] in [0, C) is checked here when the table is host-visible (pinned) and is
+ * the caller's duty otherwise, as for the other joint tables (a workgroup whose entry is out of range writes nothing).
+ * og_generate_limbs_fused_scored_f32 / og_generate_limbs_fused_flip_scored_f32: the K1-fused forms with that refinement INSIDE the
+ *   pairing -- every bilinear tap of the offset sampling is the refined value of its stride-4 cell, computed on the spot from the
+ *   (flip-merged-on-load) window, so the refined tensor is never built; 2-component offsets; the other arguments as the unrefined
+ *   forms.  Bit-identical to (og_flip_merge_f32 +) og_scored_offset_f32 + og_generate_limbs_fused_f32. */
+int og_scored_offset_f32(const float *hm, const float *off, int N, int C, int L, int h, int w, const int32_t *jf, int ksize,
+                         float *out, void *stream);
+int og_generate_limbs_fused_scored_f32(const float *hmps_lr, const float *offs_lr, int ksize, const float *scales_lr, int scales_mode,
+                                       const float *jitter_lr, int jitter_mode, int N, int C, int h, int w, const int32_t *jf,
+                                       const int32_t *jt, int L, int k, float thre_hmp, float min_len, float resize_factor,
+                                       float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace, size_t workspace_bytes,
+                                       void *stream);
+int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
+                                            const int32_t *limb_perm, const int32_t *reserve_mask, int ksize, int N, int C, int h,
+                                            int w, const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
+                                            float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
+                                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- a12: GreedyGroup.group_skeletons  decoder/group.py:39-185 (+ :187-240) ----
  * One workgroup per image, device resident (replaces .cpu().numpy() + Pool.starmap,
  * decoder/factory.py:91-94).

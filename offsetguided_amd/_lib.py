@@ -33,6 +33,9 @@ SIGNATURES = {
     "og_nms_topk_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "og_generate_limbs_fused_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_generate_limbs_fused_flip_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "og_scored_offset_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "og_generate_limbs_fused_scored_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "og_generate_limbs_fused_flip_scored_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_upsample_nms_topk_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "og_topk_workspace_bytes": (_sz, [_l, _i, _i, _i]),
     "og_collect_limbs_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
@@ -117,7 +120,7 @@ def load():
             raise ImportError(f"{LIB_PATH}: ABI version {lib.og_abi_version()} != {ABI_VERSION}; rebuild with "
                               "`python -m offsetguided_amd.build --force`")
         for name, (res, args) in SIGNATURES.items():
-            # entry points added without a version change (og_scale_accumulate_f32: the ABI only grew) -- a library built before
+            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32: the ABI only grew) -- a library built before
             # them says so here instead of with a bare AttributeError
             if not hasattr(lib, name):
                 raise ImportError(f"{LIB_PATH} lacks {name}: stale build; rebuild with `python -m offsetguided_amd.build --force`")

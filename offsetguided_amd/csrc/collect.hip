@@ -18,7 +18,31 @@ collect_limbs_kernel(const float *__restrict__ scores, const int64_t *__restrict
                                        inds + ((size_t)n * a.C + ct) * a.K, sm);
 }
 
+__global__ void __launch_bounds__(64)
+collect_limbs_scored_kernel(const float *__restrict__ scores, const int64_t *__restrict__ inds, og_collect::ScoredArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = blockIdx.x / a.L, l = blockIdx.x % a.L;
+    const int cf = a.jf[l], ct = a.jt[l];
+    og_collect::limb_rows<2, int64_t>(a, n, l, threadIdx.x, scores + ((size_t)n * a.C + cf) * a.K,
+                                      inds + ((size_t)n * a.C + cf) * a.K, scores + ((size_t)n * a.C + ct) * a.K,
+                                      inds + ((size_t)n * a.C + ct) * a.K, sm);
+}
+
 }  // namespace
+
+int og_collect_limbs_scored_impl(const char *name, const float *scores, const int64_t *inds, int N, const og_collect::ScoredArgs &a,
+                                 void *stream)
+{
+    OG_REQUIRE(scores && inds && a.offs && a.score_hm && a.jf && a.jt && a.limbs, OG_EINVAL, "%s: null pointer", name);
+    OG_REQUIRE(a.off_lowres && a.H % 4 == 0 && a.W % 4 == 0, OG_EINVAL, "%s: H,W must be multiples of 4", name);
+    OG_REQUIRE((long)a.H * a.W < (1l << 31), OG_EINVAL, "%s: plane too large", name);
+    OG_REQUIRE(a.K <= 2048, OG_EUNSUPPORTED, "%s: k=%d too large", name, a.K);
+    hipLaunchKernelGGL(collect_limbs_scored_kernel, dim3(N * a.L), dim3(64), (size_t)((a.K + 3) & ~3) * 16, (hipStream_t)stream, scores,
+                       inds, a);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
 
 OG_API int og_collect_limbs_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
                                 int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,

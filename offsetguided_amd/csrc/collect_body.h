@@ -73,14 +73,48 @@ struct Args {
     // sign = -1 for the x component, or a alone for the limbs of `reserve` -- the values og_flip_merge_f32 would have written
     const int32_t *limb_perm = nullptr, *reserve = nullptr;
     int flip_N = 0;
+    static constexpr bool kScored = false;
 };
+
+// scored_off (reference decoder/offset.py:8-43) inside the sampling: off_lowres, 2 components.  Every bilinear tap is the REFINED
+// offset of its stride-4 cell, computed on the spot with the arithmetic of og_scored_offset_f32 (csrc/scored_offset.hip) from the
+// window's heat-map and offset cells -- flip-merged on load, as og_flip_merge_f32 writes them, when flip_N > 0 -- so the refined
+// tensor is never built.  A type of its own: the kernels instantiated on Args do not see these fields.
+struct ScoredArgs : Args {
+    const float *score_hm;     // stride-4 heat maps (N, C, H/4, W/4); with flip_N > 0 (2N, C, H/4, W/4) = [images | mirrored images]
+    int score_ks;              // odd window, 1..7
+    const int32_t *kp_perm;    // flip_N > 0: config.heatmap_hflip, the mirrored image's plane of joint c is kp_perm[c]
+    static constexpr bool kScored = true;
+};
+
+// Refined offsets (both components: they share the denominator) of one stride-4 cell.  hm(y, x) and of(c, y, x) read the (merged)
+// maps.  Products are rounded before they are summed (no FMA); the sums start at +0 and take the in-bounds cells row-major.
+template <class HM, class OF>
+__device__ __forceinline__ void scored_cell(HM hm, OF of, int h, int w, int y, int x, int p, float &r0, float &r1)
+{
+    const int ya = y - p < 0 ? 0 : y - p, yb = y + p > h - 1 ? h - 1 : y + p;
+    const int xa = x - p < 0 ? 0 : x - p, xb = x + p > w - 1 ? w - 1 : x + p;
+    float den = 0.f, n0 = 0.f, n1 = 0.f;
+    for (int yy = ya; yy <= yb; ++yy)
+        for (int xx = xa; xx <= xb; ++xx) {
+            const float m = hm(yy, xx);
+            const float q0 = m * of(0, yy, xx), q1 = m * of(1, yy, xx);
+            den += m;
+            n0 += q0;
+            n1 += q1;
+        }
+    const float d = den + 1e-6f;
+    r0 = n0 / d;
+    r1 = n1 / d;
+}
 
 // Rows of limb type `l` of image `n` by one GROUP of lanes (a wave, or half a wave when K <= 32; `lane` = 0..GROUP-1
 // within the group, the groups of a wave may work on different limb types).  sf/idf and st/idt: the k best (score, flat
 // index) of the limb's from- and to-joint planes (any address space; IdxT = int64_t in global memory, int in LDS).
 // `sm`: group-private LDS scratch of 16 bytes x ((K + 3) & ~3), 16-byte aligned.
-template <int ND, class IdxT, int GROUP = 64>
-__device__ __forceinline__ void limb_rows(const Args &a, int n, int l, int lane, const float *sf, const IdxT *idf,
+// ArgsT = ScoredArgs: the compile-time variant whose offset taps are refined on the spot (scored_cell).
+template <int ND, class IdxT, int GROUP = 64, class ArgsT = Args>
+__device__ __forceinline__ void limb_rows(const ArgsT &a, int n, int l, int lane, const float *sf, const IdxT *idf,
                                           const float *st, const IdxT *idt, float *sm)
 {
     const int C = a.C, H = a.H, W = a.W, L = a.L, K = a.K;
@@ -112,7 +146,41 @@ __device__ __forceinline__ void limb_rows(const Args &a, int n, int l, int lane,
     // The offset gather of the lane's FIRST from-candidate (two dependent round trips: candidate index, then the offset
     // taps in a tensor that is cold by now) is issued before the to-candidates are staged, so the two latencies overlap.
     auto gather_offsets = [&](int64_t id, int yi, int xi, float (&o4)[ND]) {   // offset at the ORIGINAL flat index (collect.py:143-147)
-        if (off_lowres && a.flip_N > 0) {
+        if constexpr (ArgsT::kScored) {
+            static_assert(ND == 2, "scored_off needs 2-component offsets");
+            const int h4 = H / 4, w4 = W / 4, p = (a.score_ks - 1) / 2;
+            const size_t hw4 = (size_t)h4 * w4;
+            const bool flip = a.flip_N > 0, keep = flip && a.reserve[l] != 0;
+            const float *ha = a.score_hm + ((size_t)n * C + cf) * hw4, *pa = offs + ((size_t)n * 2 * L + 2 * l) * hw4;
+            const float *hb = ha, *pb = pa;
+            if (flip) {
+                hb = a.score_hm + ((size_t)(n + a.flip_N) * C + a.kp_perm[cf]) * hw4;
+                pb = offs + ((size_t)(n + a.flip_N) * 2 * L + 2 * a.limb_perm[l]) * hw4;
+            }
+            auto hm_at = [&](int y, int x) {
+                const float av = ha[(size_t)y * w4 + x];
+                if (!flip) return av;
+                return (av + hb[(size_t)y * w4 + (w4 - 1 - x)]) / 2.f;
+            };
+            auto off_at = [&](int c, int y, int x) {
+                const float av = pa[(size_t)c * hw4 + (size_t)y * w4 + x];
+                if (!flip || keep) return av;
+                return (av + pb[(size_t)c * hw4 + (size_t)y * w4 + (w4 - 1 - x)] * (c == 0 ? -1.f : 1.f)) / 2.f;
+            };
+            int x0, x1, y0, y1;
+            float lx0, lx1, ly0, ly1, t00[2], t01[2], t10[2], t11[2];
+            lin_coord(xi, w4, x0, x1, lx0, lx1);
+            lin_coord(yi, h4, y0, y1, ly0, ly1);
+            scored_cell(hm_at, off_at, h4, w4, y0, x0, p, t00[0], t00[1]);
+            scored_cell(hm_at, off_at, h4, w4, y0, x1, p, t01[0], t01[1]);
+            scored_cell(hm_at, off_at, h4, w4, y1, x0, p, t10[0], t10[1]);
+            scored_cell(hm_at, off_at, h4, w4, y1, x1, p, t11[0], t11[1]);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {       // the fma chain of bilinear4_at
+                const float ta = __builtin_fmaf(t00[c], lx0, t01[c] * lx1), tb = __builtin_fmaf(t10[c], lx0, t11[c] * lx1);
+                o4[c] = __builtin_fmaf(ta, ly0, tb * ly1);
+            }
+        } else if (off_lowres && a.flip_N > 0) {
             const int h4 = H / 4, w4 = W / 4;
             const size_t hw4 = (size_t)h4 * w4;
             const bool keep = a.reserve[l] != 0;
@@ -241,3 +309,8 @@ __device__ __forceinline__ void limb_rows(const Args &a, int n, int l, int lane,
 }
 
 }  // namespace og_collect
+
+// csrc/collect.hip, for og_generate_limbs_fused*_scored_f32 (csrc/nms_topk.hip) on shapes whose merge-and-pair stage does not fit
+// the LDS: og_collect_limbs_full_f32 with the refined sampling (a.offs = the stride-4 offsets, 2 components).
+int og_collect_limbs_scored_impl(const char *name, const float *scores, const int64_t *inds, int N, const og_collect::ScoredArgs &a,
+                                 void *stream);

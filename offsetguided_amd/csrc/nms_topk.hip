@@ -861,16 +861,15 @@ merge_bands_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ his
 // workspace.  A plane is merged by every limb that uses it (2.2 times on the COCO skeleton): 4 KB of L2 reads each, against
 // a launch, a launch gap and a round trip of the lists through memory.
 // FUSED: `in` = the stride-4 heat maps (the zero-fill path of merge_plane evaluates the x4 bicubic at single points).
-template <int ND, bool FUSED = false>
-__global__ void __launch_bounds__(512)
-merge_collect_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
-                     uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
-                     int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, og_collect::Args a, int NL,
-                     FlipSrc fs)
+// The body is shared by merge_collect_kernel (the pairing of og_collect::Args, unchanged) and merge_collect_scored_kernel (ArgsT =
+// og_collect::ScoredArgs: scored_off, the offset taps refined on the spot); lds64 / s_bound / s_nf are the kernel's LDS.
+template <int ND, bool FUSED, class ArgsT>
+__device__ __forceinline__ void
+merge_collect_body(uint64_t *lds64, uint64_t *s_bound, int *s_nf, const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
+                   uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, const BandMap &bm, int max_bands,
+                   int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, const ArgsT &a, int NL,
+                   const FlipSrc &fs)
 {
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
-    __shared__ uint64_t s_bound[2];
-    __shared__ int s_nf[2];
     MERGE_STAMP(0);
     const int planes = bm.planes, k = a.K, H = a.H, W = a.W, n_all = max_bands * wl * k, Kp = (k + 3) & ~3;   // n_all: LDS carve-up
     const int half = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -908,8 +907,37 @@ merge_collect_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ h
     if (!limb) return;
     __syncthreads();
     MERGE_STAMP(1);
-    if (threadIdx.x < 64) og_collect::limb_rows<ND, int>(a, n, l, threadIdx.x, ls, li, ls + Kp, li + Kp, sm);
+    if (threadIdx.x < 64) og_collect::limb_rows<ND, int, 64, ArgsT>(a, n, l, threadIdx.x, ls, li, ls + Kp, li + Kp, sm);
     MERGE_STAMP(2);
+}
+
+template <int ND, bool FUSED = false>
+__global__ void __launch_bounds__(512)
+merge_collect_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
+                     uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
+                     int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, og_collect::Args a, int NL,
+                     FlipSrc fs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
+    __shared__ uint64_t s_bound[2];
+    __shared__ int s_nf[2];
+    merge_collect_body<ND, FUSED>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
+                                  out_inds, a, NL, fs);
+}
+
+// scored_off: the same launch with the refined offset sampling (2-component offsets sampled from the stride-4 map)
+template <bool FUSED>
+__global__ void __launch_bounds__(512)
+merge_collect_scored_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
+                            uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
+                            int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds,
+                            og_collect::ScoredArgs a, int NL, FlipSrc fs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
+    __shared__ uint64_t s_bound[2];
+    __shared__ int s_nf[2];
+    merge_collect_body<2, FUSED>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
+                                 out_inds, a, NL, fs);
 }
 
 struct Plan {
@@ -973,6 +1001,9 @@ bool make_plan(long planes, int H, int W, int k, bool aligned16, Plan *p)
 struct Pairing {   // og_generate_limbs_f32: the merge launch pairs the limbs as well
     og_collect::Args a;
     int nd, N;
+    const float *score_hm = nullptr;     // scored_off (og_collect::ScoredArgs): score_ks > 0 selects merge_collect_scored_kernel
+    int score_ks = 0;
+    const int32_t *kp_perm = nullptr;
 };
 
 template <bool NMS_MODE, bool FUSED = false>
@@ -1034,9 +1065,16 @@ int run_topk(const float *in, long planes, int H, int W, int k, float *out_score
         const size_t plds = 2 * mlds + (size_t)((k + 3) & ~3) * 32;
         if (pair && plds <= kDynLdsLimit) {
             const int NL = pair->N * pair->a.L;
-            auto kern = pair->nd == 2 ? merge_collect_kernel<2, FUSED> : merge_collect_kernel<4, FUSED>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds, stream, keys, hist, magic,
-                               p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, pair->a, NL, fs);
+            if (pair->score_ks > 0) {
+                const og_collect::ScoredArgs sa{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm};
+                hipLaunchKernelGGL((merge_collect_scored_kernel<FUSED>), dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds,
+                                   stream, keys, hist, magic, p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, sa, NL,
+                                   fs);
+            } else {
+                auto kern = pair->nd == 2 ? merge_collect_kernel<2, FUSED> : merge_collect_kernel<4, FUSED>;
+                hipLaunchKernelGGL(kern, dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds, stream, keys, hist, magic,
+                                   p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, pair->a, NL, fs);
+            }
             OG_LAUNCH_CHECK(name);
             return 1;   // paired
         }
@@ -1132,8 +1170,13 @@ static int generate_limbs_impl(const char *name, const float *hmps_hr, const flo
                                float thre_hmp, float min_len, float resize_factor, float *topk_scores,
                                int64_t *topk_inds, float *limbs, const int32_t *limb_perm, const int32_t *reserve_mask,
                                void *workspace, size_t workspace_bytes, void *stream, bool hm_lowres = false,
-                               const int32_t *kp_perm = nullptr)
+                               const int32_t *kp_perm = nullptr, int score_ks = 0)
 {
+    // score_ks > 0 (hm_lowres forms only): scored_off, the offset taps refined from the stride-4 heat maps = hmps_hr itself
+    OG_REQUIRE(score_ks == 0 || (score_ks >= 1 && score_ks <= 7 && score_ks % 2 == 1), OG_EINVAL,
+               "%s: ksize must be odd, 1..7 (got %d)", name, score_ks);
+    OG_REQUIRE(score_ks == 0 || (hm_lowres && off_is_lowres && vector_nd == 2), OG_EUNSUPPORTED,
+               "%s: scored offsets need the stride-4 maps and 2-component offsets", name);
     OG_REQUIRE(hmps_hr && offs && jf && jt && limbs && workspace, OG_EINVAL, "%s: null pointer", name);
     OG_REQUIRE((topk_scores == nullptr) == (topk_inds == nullptr), OG_EINVAL, "%s: topk_scores and topk_inds go together", name);
     OG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && L > 0 && k > 0, OG_EINVAL, "%s: bad shape", name);
@@ -1161,7 +1204,7 @@ static int generate_limbs_impl(const char *name, const float *hmps_hr, const flo
     const size_t topk = og_align_up(og_topk_workspace_bytes((long)N * C, H, W, k), 256);
     float *sc = own_lists ? reinterpret_cast<float *>(ws2 + topk + (size_t)N * C * k * 8) : topk_scores;
     int64_t *id = own_lists ? reinterpret_cast<int64_t *>(ws2 + topk) : topk_inds;
-    const Pairing pr{ca, vector_nd, N};
+    const Pairing pr{ca, vector_nd, N, score_ks > 0 ? hmps_hr : nullptr, score_ks, kp_perm};
     const bool can_pair = (long)H * W < (1l << 31) && k <= 2048;
     OG_REQUIRE(!hm_lowres || (H % 4 == 0 && W % 4 == 0), OG_EINVAL, "%s: H,W must be multiples of 4", name);
     const int rc = hm_lowres ? run_topk<true, true>(hmps_hr, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
@@ -1171,6 +1214,8 @@ static int generate_limbs_impl(const char *name, const float *hmps_hr, const flo
     if (rc < 0 || rc == 1) return rc < 0 ? rc : OG_OK;
     // (shapes whose merge + pairing stage does not fit the LDS: the lists are complete, pair them with the collect kernel)
     OG_REQUIRE(!limb_perm, OG_EUNSUPPORTED, "%s: k = %d is too large for the merge-and-pair stage of the flip-folded form", name, k);
+    if (score_ks > 0)
+        return og_collect_limbs_scored_impl(name, sc, id, N, og_collect::ScoredArgs{ca, hmps_hr, score_ks, nullptr}, stream);
     return og_collect_limbs_full_f32(sc, id, offs, off_is_lowres, vector_nd, scales, scales_mode, jitter, jitter_mode, N, C,
                                      H, W, jf, jt, L, k, thre_hmp, min_len, resize_factor, limbs, stream);
 }
@@ -1234,6 +1279,40 @@ OG_API int og_generate_limbs_fused_flip_f32(const float *hm_pair_lr, const int32
     return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, nullptr, 0, nullptr, 0, N, C, 4 * h, 4 * w, jf, jt, L, k, thre_hmp,
                                min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace,
                                workspace_bytes, stream, true, kp_perm);
+}
+
+// ---- scored_off inside the pairing: the two K1-fused forms with every offset tap refined on the spot (og_collect::ScoredArgs,
+// collect_body.h) from the stride-4 heat maps they already take; bit-identical to og_scored_offset_f32 (after og_flip_merge_f32,
+// for the flip form) in front of the unrefined entry point.
+OG_API int og_generate_limbs_fused_scored_f32(const float *hmps_lr, const float *offs_lr, int ksize, const float *scales_lr,
+                                              int scales_mode, const float *jitter_lr, int jitter_mode, int N, int C, int h, int w,
+                                              const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
+                                              float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
+                                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "og_generate_limbs_fused_scored_f32";
+    OG_REQUIRE(ksize >= 1 && ksize <= 7 && ksize % 2 == 1, OG_EINVAL, "%s: ksize must be odd, 1..7 (got %d)", name, ksize);
+    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
+    OG_REQUIRE(scales_mode == 0 || scales_mode >= 2, OG_EINVAL, "%s: the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
+    OG_REQUIRE(jitter_mode == 0 || jitter_mode == 3, OG_EINVAL, "%s: the jitter maps are the stride-4 head output (jitter_mode 3)", name);
+    return generate_limbs_impl(name, hmps_lr, offs_lr, 1, 2, scales_lr, scales_mode, jitter_lr, jitter_mode, N, C, 4 * h, 4 * w, jf, jt, L,
+                               k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds, limbs, nullptr, nullptr, workspace,
+                               workspace_bytes, stream, true, nullptr, ksize);
+}
+
+OG_API int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
+                                                   const int32_t *limb_perm, const int32_t *reserve_mask, int ksize, int N, int C,
+                                                   int h, int w, const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp,
+                                                   float min_len, float resize_factor, float *topk_scores, int64_t *topk_inds,
+                                                   float *limbs, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "og_generate_limbs_fused_flip_scored_f32";
+    OG_REQUIRE(ksize >= 1 && ksize <= 7 && ksize % 2 == 1, OG_EINVAL, "%s: ksize must be odd, 1..7 (got %d)", name, ksize);
+    OG_REQUIRE(kp_perm && limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
+    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
+    return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, nullptr, 0, nullptr, 0, N, C, 4 * h, 4 * w, jf, jt, L, k, thre_hmp,
+                               min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace,
+                               workspace_bytes, stream, true, kp_perm, ksize);
 }
 
 #ifdef OG_K1_STAMPS

@@ -91,11 +91,12 @@ class LimbsCollect(object):
                 float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
         return limbs
 
-    def generate_limbs_fused_flip(self, hm_pair_lr, offs_pair_lr, kp_perm, limb_perm, reserve_mask):
+    def generate_limbs_fused_flip(self, hm_pair_lr, offs_pair_lr, kp_perm, limb_perm, reserve_mask, scored_ks=0):
         """generate_limbs_fused on the flip-merged maps WITHOUT merging them first (og_generate_limbs_fused_flip_f32): the stride-4
         head outputs of [images | mirrored images], (2N, C, h, w) and (2N, 2L, h, w); every heat-map source value and every offset tap
         is computed as PostProcess.flip_augment would have written it (decoder/factory.py:98-146).  2-component offsets, no scale /
-        jitter head."""
+        jitter head.  scored_ks > 0: scored_off with that window, every offset tap refined inside the pairing
+        (og_generate_limbs_fused_flip_scored_f32); 0 = the unrefined call."""
         hm = _lib.require_device(hm_pair_lr, 'hmps')
         offs = _lib.require_device(offs_pair_lr, 'offs')
         n2, c, h, w = hm.shape
@@ -106,23 +107,29 @@ class LimbsCollect(object):
         jf, jt = _lib.int_table(self.jtypes_f, dev), _lib.int_table(self.jtypes_t, dev)
         with _lib.stage_timer('k1f_fused_limbs', dev):
             ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, 4 * h, 4 * w, self.K), 'limbs')   # zero-filled
-            _lib.check(lib.og_generate_limbs_fused_flip_f32(
-                _lib.ptr(hm), _lib.ptr(_lib.int_table(kp_perm, dev)), _lib.ptr(offs), _lib.ptr(_lib.int_table(limb_perm, dev)),
-                _lib.ptr(_lib.int_table(reserve_mask, dev)), n, c, h, w, _lib.ptr(jf), _lib.ptr(jt), n_limbs, self.K,
-                float(self.thre_hmp), float(self.min_len), float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws),
-                ws.numel(), _lib.stream_ptr(dev)), lib)
+            tables = (_lib.ptr(hm), _lib.ptr(_lib.int_table(kp_perm, dev)), _lib.ptr(offs), _lib.ptr(_lib.int_table(limb_perm, dev)),
+                      _lib.ptr(_lib.int_table(reserve_mask, dev)))
+            rest = (n, c, h, w, _lib.ptr(jf), _lib.ptr(jt), n_limbs, self.K, float(self.thre_hmp), float(self.min_len),
+                    float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+            if scored_ks:
+                _lib.check(lib.og_generate_limbs_fused_flip_scored_f32(*tables, int(scored_ks), *rest), lib)
+            else:
+                _lib.check(lib.og_generate_limbs_fused_flip_f32(*tables, *rest), lib)
         return limbs
 
-    def generate_limbs_fused(self, hmps_lr, offs_lr, vector_nd=2, scmps_lr=None, scale_inter='bicubic', jomps_lr=None):
+    def generate_limbs_fused(self, hmps_lr, offs_lr, vector_nd=2, scmps_lr=None, scale_inter='bicubic', jomps_lr=None, scored_ks=0):
         """Same limbs as generate_limbs(F.interpolate(hmps_lr, x4, 'bicubic'), [], F.interpolate(offs_lr, x4,
-        'bilinear'), []) with NEITHER hi-res tensor built: K1-fused upsamples inside the NMS kernel."""
+        'bilinear'), []) with NEITHER hi-res tensor built: K1-fused upsamples inside the NMS kernel.  scored_ks > 0: scored_off
+        with that window, every offset tap refined inside the pairing (og_generate_limbs_fused_scored_f32); 0 = the unrefined call."""
         assert hmps_lr.shape[-2:] == offs_lr.shape[-2:], 'spatial resolution should be equal'
+        if scored_ks and vector_nd != 2:
+            raise NotImplementedError('scored_off needs 2-component offsets (the reference fails here as well)')
         return self._collect(hmps_lr, offs_lr, off_is_lowres=True, hm_is_lowres=True, vector_nd=vector_nd,
                              scales=scmps_lr, scales_mode=2 if scale_inter == 'bicubic' else 3,
-                             jitter=self._jitter(jomps_lr), jitter_mode=3)
+                             jitter=self._jitter(jomps_lr), jitter_mode=3, scored_ks=scored_ks)
 
     def _collect(self, hmps_hr, offs, off_is_lowres, hm_is_lowres=False, vector_nd=2, scales=None, scales_mode=0,
-                 jitter=None, jitter_mode=0):
+                 jitter=None, jitter_mode=0, scored_ks=0):
         hmps_hr = _lib.require_device(hmps_hr, 'hmps_hr')
         offs = _lib.require_device(offs, 'offs')
         n, c, h, w = hmps_hr.shape
@@ -165,8 +172,10 @@ class LimbsCollect(object):
                 return limbs
             # K1-fused: the x4 bicubic runs inside the NMS kernel; ONE C call = two launches (band top-k; merge + pairing)
             ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, h, w, self.K), 'limbs')   # zero-filled
-            _lib.check(lib.og_generate_limbs_fused_f32(
-                _lib.ptr(hmps_hr), _lib.ptr(offs), int(vector_nd), _lib.ptr(scales) if scales is not None else None, int(scales_mode),
+            # (the scored form takes the window where the unrefined one takes vector_nd: its offsets have 2 components)
+            entry = lib.og_generate_limbs_fused_scored_f32 if scored_ks else lib.og_generate_limbs_fused_f32
+            _lib.check(entry(
+                _lib.ptr(hmps_hr), _lib.ptr(offs), int(scored_ks or vector_nd), _lib.ptr(scales) if scales is not None else None, int(scales_mode),
                 _lib.ptr(jitter) if jitter is not None else None, int(jitter_mode), n, c, h // 4, w // 4, _lib.ptr(jf), _lib.ptr(jt),
                 n_limbs, self.K, float(self.thre_hmp), float(self.min_len), float(self.resize_factor), None, None,
                 _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)

@@ -20,7 +20,7 @@ from ..config.coco_data import (COCO_KEYPOINTS, COCO_PERSON_SKELETON, COCO_PERSO
 from ..utils import boolean_string
 from .collect import LimbsCollect
 from .group import GreedyGroup
-from .offset import pack_jtypes, scored_offset
+from .offset import pack_jtypes, scored_offset_device
 
 LOG = logging.getLogger(__name__)
 
@@ -142,6 +142,10 @@ class PostProcess(torch.nn.Module):
         # flip-test (2-component offsets, no scale / jitter head): flip_augment's merge rides on the loads of K1a and on the
         # offset sampling of K1 instead of running as its own pass (K0, og_flip_merge_f32); identical results
         self.fold_flip = os.environ.get('OG_FOLD_FLIP', '1') != '0'
+        # scored_off: the window of the heatmap-weighted offset refinement (the reference hard-codes 3 at its call site,
+        # decoder/factory.py:70-72).  K1-fused refines every offset tap inside the pairing; fused_upsample=False runs
+        # og_scored_offset_f32 in front of the unchanged K1a + K1
+        self.scored_kernel_size = 3
         # submit(): grouping (one workgroup per image, latency-bound) and the pose D2H copy run on their own stream, so
         # the caller's next launches (the following batch's backbone) do not queue behind them
         self.group_on_side_stream = True   # (an attribute, no longer an environment switch: measured best since round 2)
@@ -235,14 +239,17 @@ class PostProcess(torch.nn.Module):
         offs = out_offsets[self.feat_stage]
         scmps = out_scales[self.feat_stage]
         vector_nd = 2
-        if (flip_test and self.fold_flip and not cat_flip_offs and not scored_off
+        scored_ks = self.scored_kernel_size if scored_off else 0
+        # (scored_off without K1-fused takes the unfolded route: the roofline-mode forms have no refined variant)
+        if (flip_test and self.fold_flip and not cat_flip_offs and not (scored_off and not self.fused_upsample)
                 and self.inter_mode == 'bicubic' and not (self.include_scale and isinstance(scmps, torch.Tensor))
                 and not (self.include_jitter_offset and isinstance(jomps, torch.Tensor))):
             n_limbs = offs.shape[1] // 2
             keep = [1 if l in self.limbs_flips[1] else 0 for l in range(n_limbs)]
             if self.fused_upsample:
                 try:
-                    return self.limb_collect.generate_limbs_fused_flip(hmps, offs, self.keypoints_flips, self.limbs_flips[0], keep)
+                    return self.limb_collect.generate_limbs_fused_flip(hmps, offs, self.keypoints_flips, self.limbs_flips[0], keep,
+                                                                       scored_ks=scored_ks)
                 except _lib.OgError as e:
                     # merge + pairing of the folded form keeps a plane's lists in LDS: beyond k ~ 226 at 640 x 640 (half that for inputs
                     # twice as tall) it does not fit and the C side says OG_EUNSUPPORTED.  The unfolded route below (flip_augment as its own
@@ -254,17 +261,18 @@ class PostProcess(torch.nn.Module):
                 return self.limb_collect.generate_limbs_flip(hmps_hr, offs, self.limbs_flips[0], keep)
         if flip_test:
             hmps, jomps, offs, scmps, vector_nd = self.flip_augment(hmps, jomps, offs, scmps, cat_flip_offs, vector_nd)
+        fused = self.fused_upsample and self.inter_mode == 'bicubic'
         if scored_off:
             if vector_nd != 2:
                 raise NotImplementedError('scored_off needs 2-component offsets (the reference fails here as well)')
-            jf, jt = pack_jtypes(self.skeleton)
-            offs = scored_offset(hmps.float(), offs.float(), jf, jt, kernel_size=3)
+            if not fused:   # K1a + K1 materialise tensors anyway: the refined offsets are one more of them (og_scored_offset_f32)
+                offs = scored_offset_device(hmps, offs, pack_jtypes(self.skeleton)[0], self.scored_kernel_size)
         # keypoint-scale head: sampled at the peaks from the stride-4 map, as F.interpolate(mode=inter_mode) would give
         scl = scmps.float().contiguous() if self.include_scale and isinstance(scmps, torch.Tensor) else None
         # jitter-offset head: bilinear x4 (factory.py:84-88), sampled where K2 needs it
         jit = jomps.float().contiguous() if self.include_jitter_offset and isinstance(jomps, torch.Tensor) else None
-        if self.fused_upsample and self.inter_mode == 'bicubic':
-            return self.limb_collect.generate_limbs_fused(hmps, offs, vector_nd, scl, self.inter_mode, jit)
+        if fused:
+            return self.limb_collect.generate_limbs_fused(hmps, offs, vector_nd, scl, self.inter_mode, jit, scored_ks=scored_ks)
         hmps_hr = upsample4(hmps, self.inter_mode)
         return self.limb_collect.generate_limbs_lowres(hmps_hr, offs, vector_nd, scl, self.inter_mode, jit)
 

@@ -7,7 +7,8 @@ scale_affines: the per-image table (Ax, Bx, Ay, By, inv_ax, inv_ay) that maps a 
 metas the input chain wrote (transforms.EvalPreprocess.multi_scale): base cell centre -> original image (annotations_inverse) ->
 scale-s input (rescale + pad) -> scale-s grid.  merge_scales: one og_scale_accumulate_f32 launch per scale into base-grid accumulators.
 
-Not served together with more than one scale (NotImplementedError): cat_flip_offs, scored_off, the keypoint-scale and jitter-offset
+scored_off (--scored-off) composes: after the merge the decode is the ordinary one, refinement inside the pairing included.
+Not served together with more than one scale (NotImplementedError): cat_flip_offs, the keypoint-scale and jitter-offset
 heads (include_scale / use_jitter_offset maps) and --fixed-height (RightDownPad metas)."""
 import numpy as np
 import torch

@@ -46,6 +46,9 @@ def evaluate_cli(argv=None):
     parser.add_argument('--fixed-height', action='store_true', default=False)
     parser.add_argument('--flip-test', action='store_true', default=False, help='flip augmentation during testing')
     parser.add_argument('--cat-flip-offset', action='store_true', default=False)
+    parser.add_argument('--scored-off', action='store_true', default=False,
+                        help='heatmap-weighted refinement of the guiding offsets (generate_poses(scored_off=True); beyond the '
+                             'reference command line, which never passes the switch)')
     parser.add_argument('--test-scales', default=[1.0], type=float, nargs='+', metavar='S',
                         help='multi-scale test (beyond the reference): input scales relative to --long-edge whose head outputs are '
                              'averaged on the grid of scale 1 (which must be in the list) and decoded once')
@@ -245,6 +248,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     # multi-scale test (--test-scales with more than one scale; decoder/multiscale.py): per batch and scale the input chain
     # (EvalPreprocess.multi_scale: one H2D copy, one launch per scale), the engine of that scale's shape, then one og_scale_accumulate_f32
     # launch per scale into the lane's base-grid accumulators and one submit of the averaged maps.  [1.0] runs the code above unchanged.
+    scored_off = bool(getattr(args, 'scored_off', False))
     scales = validate_test_scales(getattr(args, 'test_scales', [1.0]), getattr(args, 'fixed_height', False),
                                   getattr(args, 'cat_flip_offset', False))
     multi = len(scales) > 1
@@ -310,7 +314,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
             empty = [[] for _ in range(slot[0].n_stacks)]
             feats = [([accumulators[lane][0]] * len(empty), list(empty), list(empty)),
                      ([accumulators[lane][1]] * len(empty), list(empty), list(empty))]
-            return (proc.submit(feats, flip_test=False), base_metas)
+            return (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas)
 
     try:
         for batch_idx, ((images, _, metas), packed) in enumerate(ahead(data_loader)):
@@ -339,7 +343,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     lanes[lane].wait_event(slot[2])              # the engine's last batch (maybe on another lane): its decoder has read the outputs
                 with torch.cuda.stream(lanes[lane]):
                     outputs = slot[0](images)
-                    handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset), metas)
+                    handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset,
+                                                      scored_off=scored_off), metas)
                     slot[1], slot[2] = batch_idx, torch.cuda.Event()
                     slot[2].record(lanes[lane])
             pending.append(handle)
