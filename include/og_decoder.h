@@ -58,6 +58,11 @@ int og_upsample_bilinear4_f32(const float *src, long planes, int h, int w, float
  * out = heat * (maxpool3x3(zero-padded heat) == heat); heat/out (planes,H,W). */
 int og_hmp_nms_f32(const float *heat, long planes, int H, int W, float *out, void *stream);
 
+/* Same with another window: out = heat * (maxpool_kernel(zero-padded heat) == heat), kernel odd, 1..7 (OG_EUNSUPPORTED otherwise).
+ * Exact compares; the zero padding takes part in the maximum; a suppressed element is heat * 0 (it keeps the sign of its input).
+ * One launch, 64 x 16 tiles with their halo staged in LDS. */
+int og_hmp_nms_k_f32(const float *heat, long planes, int H, int W, int kernel, float *out, void *stream);
+
 /* ---- a7: topK_channel  decoder/heatmap.py:38-49 ----
  * Per-plane top-k of `scores` (planes, hw), sorted by value descending; ties: lower flat
  * index first (-0.0 == +0.0).  Outputs scores (planes,k) f32 and inds (planes,k) i64; the
@@ -206,6 +211,19 @@ int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, const int32
                                             float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
                                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* The flip form with the optional heads folded in as well: scales_pair_lr (2N,C,h,w) with scales_mode 2 / 3 and / or jitter_pair_lr
+ * (2N,2,h,w) with jitter_mode 3 (square inputs, as og_generate_limbs_fused_f32), the head outputs of [images | mirrored images]; at
+ * least one of them.  Every scale / jitter tap is the value og_flip_merge_heads_f32 would have written.  ksize 0: unrefined offsets;
+ * odd 1..7: scored_off as og_generate_limbs_fused_flip_scored_f32.  Bit-identical to og_flip_merge_f32 + og_flip_merge_heads_f32 +
+ * og_generate_limbs_fused_f32 / _scored_f32; a kernel instantiation of its own (the forms above keep their registers and LDS).
+ * OG_EUNSUPPORTED when the merge-and-pair stage does not fit the LDS (large k), as the other flip forms: take the unfolded route. */
+int og_generate_limbs_fused_flip_heads_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
+                                           const int32_t *limb_perm, const int32_t *reserve_mask, int ksize,
+                                           const float *scales_pair_lr, int scales_mode, const float *jitter_pair_lr, int jitter_mode,
+                                           int N, int C, int h, int w, const int32_t *jf, const int32_t *jt, int L, int k,
+                                           float thre_hmp, float min_len, float resize_factor, float *topk_scores, int64_t *topk_inds,
+                                           float *limbs, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- a12: GreedyGroup.group_skeletons  decoder/group.py:39-185 (+ :187-240) ----
  * One workgroup per image, device resident (replaces .cpu().numpy() + Pool.starmap,
  * decoder/factory.py:91-94).
@@ -230,6 +248,14 @@ int og_flip_merge_f32(const float *hm, const float *off, int N, int C, int L, in
                       const int32_t *kp_perm, const int32_t *limb_perm, const int32_t *reserve_mask,
                       float *hm_out, float *off_out, void *stream);
 
+/* ---- a4, the optional heads  decoder/factory.py:108-113 (jitter offsets), :141-144 (keypoint scales) ----
+ * scmps (2N,C,h,w) -> sc_out (N,C,h,w) = (scmps[:N] + flipW(scmps[N:])[:, kp_perm]) / 2;
+ * jomps (2N,2,h,w) -> jo_out (N,2,h,w) = (jomps[:N] + flipW(jomps[N:] with channel 0 = x negated)) / 2, no permutation.
+ * Either head may be NULL together with its output (not both); kp_perm int32[C] device array, needed with scmps.  The sum is
+ * taken first and halved after, bit-identical to the torch expressions above.  One launch for both maps. */
+int og_flip_merge_heads_f32(const float *scmps, const float *jomps, int N, int C, int h, int w, const int32_t *kp_perm,
+                            float *sc_out, float *jo_out, void *stream);
+
 /* ---- a4, cat_flip_offs=True form  decoder/factory.py:115-127 ----
  * Same inputs; off_out (N,4L,h,w): per limb [x, y, mirrored x, mirrored y] (reserve limbs repeat x, y). */
 int og_flip_cat_f32(const float *hm, const float *off, int N, int C, int L, int h, int w,
@@ -248,6 +274,16 @@ int og_scale_accumulate_f32(const float *hm, const float *off, int N, int flip, 
                             const int32_t *kp_perm, const int32_t *limb_perm, const int32_t *reserve_mask,
                             const float *aff, int h, int w, int mode, float inv_count, float *hm_acc, float *off_acc,
                             void *stream);
+
+/* Same launch over [hm | off | scl | jit]: scl (F*N,C,hs,ws) keypoint scales and / or jit (F*N,2,hs,ws) jitter offsets, each NULL
+ * together with its accumulator scl_acc (N,C,h,w) / jit_acc (N,2,h,w).  With flip the pairs are merged as og_flip_merge_heads_f32
+ * merges them, before the resample.  Units: a jitter offset is multiplied by inv_ax (channel 0) / inv_ay (channel 1) as the guiding
+ * offsets are; a keypoint scale is a length in scale-s input pixels and is multiplied by sqrtf(inv_ax * inv_ay) (one fp32 multiply,
+ * one correctly rounded square root).  Everything else, hm_acc / off_acc included, as og_scale_accumulate_f32. */
+int og_scale_accumulate_heads_f32(const float *hm, const float *off, const float *scl, const float *jit, int N, int flip, int C,
+                                  int L, int hs, int ws, const int32_t *kp_perm, const int32_t *limb_perm,
+                                  const int32_t *reserve_mask, const float *aff, int h, int w, int mode, float inv_count,
+                                  float *hm_acc, float *off_acc, float *scl_acc, float *jit_acc, void *stream);
 
 /* ---- backbone epilogues (bf16, channels-last / NHWC activations of the inference engine) ----
  * Stand-alone epilogue / layout passes.  In the engine every convolution carries its epilogue itself (og_conv*_ below);

@@ -74,6 +74,7 @@ struct Args {
     const int32_t *limb_perm = nullptr, *reserve = nullptr;
     int flip_N = 0;
     static constexpr bool kScored = false;
+    static constexpr bool kFlipHeads = false;
 };
 
 // scored_off (reference decoder/offset.py:8-43) inside the sampling: off_lowres, 2 components.  Every bilinear tap is the REFINED
@@ -85,6 +86,17 @@ struct ScoredArgs : Args {
     int score_ks;              // odd window, 1..7
     const int32_t *kp_perm;    // flip_N > 0: config.heatmap_hflip, the mirrored image's plane of joint c is kp_perm[c]
     static constexpr bool kScored = true;
+};
+
+// flip-test with the keypoint-scale and / or jitter-offset head folded into their sampling (flip_N > 0; Base = Args or ScoredArgs):
+// scales holds (2N, C, H/4, W/4), jitter (2N, 2, H/4, W/4) = [images | mirrored images] (scale_mode 2 / 3, jitter_mode 3, either may
+// be absent); every tap reads the value og_flip_merge_heads_f32 would have written -- scale (a + b[kp_perm[c]][y][w-1-x]) / 2, jitter
+// (a + sign * b[y][w-1-x]) / 2 with sign = -1 for the x channel.  A type of its own, as ScoredArgs: the kernels instantiated on Args
+// and ScoredArgs compile the unmerged sampling only.
+template <class Base>
+struct FlipHeadsArgs : Base {
+    const int32_t *heads_kp_perm;   // config.heatmap_hflip: the mirrored image's scale plane of joint c is heads_kp_perm[c]
+    static constexpr bool kFlipHeads = true;
 };
 
 // Refined offsets (both components: they share the denominator) of one stride-4 cell.  hm(y, x) and of(c, y, x) read the (merged)
@@ -130,12 +142,28 @@ __device__ __forceinline__ void limb_rows(const ArgsT &a, int n, int l, int lane
     // as F.interpolate(x4, 'bilinear') would.  (row, col) are passed as the reference indexes them -- it reads the
     // guide-point refinement at [x][y].
     auto jitter_at = [&](int comp, int row, int col) -> float {
+        if constexpr (ArgsT::kFlipHeads) {
+            const int h4 = H / 4, w4 = W / 4;
+            const size_t hw4 = (size_t)h4 * w4;
+            const float *qa = jitter + ((size_t)n * 2 + comp) * hw4, *qb = jitter + ((size_t)(n + a.flip_N) * 2 + comp) * hw4;
+            const float sign = comp == 0 ? -1.f : 1.f;
+            return bilinear4_fn([&](int y, int x) { return (qa[(size_t)y * w4 + x] + qb[(size_t)y * w4 + (w4 - 1 - x)] * sign) / 2.f; },
+                                h4, w4, row, col);
+        }
         if (jitter_mode == 1) return jitter[((size_t)n * 2 + comp) * ((long)H * W) + (size_t)row * W + col];
         return bilinear4_at(jitter + ((size_t)n * 2 + comp) * (H / 4) * (W / 4), H / 4, W / 4, row, col);
     };
     // keypoint-scale head: the scale map of the joint's channel at the candidate's pixel
     auto scale_at = [&](int ch, long id, int yy, int xx) -> float {
         if (scale_mode == 0) return 4.f;
+        if constexpr (ArgsT::kFlipHeads) {
+            const int h4 = H / 4, w4 = W / 4;
+            const size_t hw4 = (size_t)h4 * w4;
+            const float *qa = scales + ((size_t)n * C + ch) * hw4, *qb = scales + ((size_t)(n + a.flip_N) * C + a.heads_kp_perm[ch]) * hw4;
+            if (scale_mode == 2) return og_bicubic4_at(qa, qb, h4, w4, yy, xx);
+            return bilinear4_fn([&](int y, int x) { return (qa[(size_t)y * w4 + x] + qb[(size_t)y * w4 + (w4 - 1 - x)]) / 2.f; }, h4, w4,
+                                yy, xx);
+        }
         if (scale_mode == 1) return scales[((size_t)n * C + ch) * ((long)H * W) + id];
         const float *pl = scales + ((size_t)n * C + ch) * (H / 4) * (W / 4);
         return scale_mode == 2 ? og_bicubic4_at(pl, H / 4, W / 4, yy, xx) : bilinear4_at(pl, H / 4, W / 4, yy, xx);

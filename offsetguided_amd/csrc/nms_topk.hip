@@ -40,6 +40,8 @@
 //     * rank-counting loops must read LDS wide (4 x ds_read_b128 per step, og_count_greater).
 #include <math.h>
 
+#include <type_traits>
+
 #include "bicubic.h"
 #ifdef OG_K1_STAMPS   // tuning harness: time points inside the limb pairing (value-dependent, so they cannot be hoisted)
 __device__ long long g_k1_stamps[1024 * 16];
@@ -940,6 +942,23 @@ merge_collect_scored_kernel(const uint64_t *__restrict__ band_keys, int *__restr
                                  out_inds, a, NL, fs);
 }
 
+// flip-test with the scale / jitter heads sampled from the [images | mirrored images] pairs (og_collect::FlipHeadsArgs): instantiated
+// apart from the two kernels above, which keep their registers and LDS; K1-fused only.
+template <bool SCORED>
+__global__ void __launch_bounds__(512)
+merge_collect_heads_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
+                           uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
+                           int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds,
+                           og_collect::FlipHeadsArgs<std::conditional_t<SCORED, og_collect::ScoredArgs, og_collect::Args>> a, int NL,
+                           FlipSrc fs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
+    __shared__ uint64_t s_bound[2];
+    __shared__ int s_nf[2];
+    merge_collect_body<2, true>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
+                                out_inds, a, NL, fs);
+}
+
 struct Plan {
     int vec, rows, nbands, panel_strips, nwaves, cap, t_sub;   // rows / nbands: equal bands (og_hmp_nms_f32)
     BandMap bm;       // the band kernel's work items
@@ -1004,6 +1023,7 @@ struct Pairing {   // og_generate_limbs_f32: the merge launch pairs the limbs as
     const float *score_hm = nullptr;     // scored_off (og_collect::ScoredArgs): score_ks > 0 selects merge_collect_scored_kernel
     int score_ks = 0;
     const int32_t *kp_perm = nullptr;
+    bool flip_heads = false;             // og_collect::FlipHeadsArgs (K1-fused flip form with a scale / jitter pair; kp_perm set)
 };
 
 template <bool NMS_MODE, bool FUSED = false>
@@ -1065,7 +1085,19 @@ int run_topk(const float *in, long planes, int H, int W, int k, float *out_score
         const size_t plds = 2 * mlds + (size_t)((k + 3) & ~3) * 32;
         if (pair && plds <= kDynLdsLimit) {
             const int NL = pair->N * pair->a.L;
-            if (pair->score_ks > 0) {
+            if (FUSED && pair->flip_heads) {
+                const dim3 grid((unsigned)(NL + (planes + 1) / 2));
+                if (pair->score_ks > 0) {
+                    const og_collect::FlipHeadsArgs<og_collect::ScoredArgs> ha{{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm},
+                                                                               pair->kp_perm};
+                    hipLaunchKernelGGL((merge_collect_heads_kernel<true>), grid, dim3(512), plds, stream, keys, hist, magic, p.magic, in,
+                                       p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, ha, NL, fs);
+                } else {
+                    const og_collect::FlipHeadsArgs<og_collect::Args> ha{pair->a, pair->kp_perm};
+                    hipLaunchKernelGGL((merge_collect_heads_kernel<false>), grid, dim3(512), plds, stream, keys, hist, magic, p.magic, in,
+                                       p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, ha, NL, fs);
+                }
+            } else if (pair->score_ks > 0) {
                 const og_collect::ScoredArgs sa{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm};
                 hipLaunchKernelGGL((merge_collect_scored_kernel<FUSED>), dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds,
                                    stream, keys, hist, magic, p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, sa, NL,
@@ -1170,7 +1202,7 @@ static int generate_limbs_impl(const char *name, const float *hmps_hr, const flo
                                float thre_hmp, float min_len, float resize_factor, float *topk_scores,
                                int64_t *topk_inds, float *limbs, const int32_t *limb_perm, const int32_t *reserve_mask,
                                void *workspace, size_t workspace_bytes, void *stream, bool hm_lowres = false,
-                               const int32_t *kp_perm = nullptr, int score_ks = 0)
+                               const int32_t *kp_perm = nullptr, int score_ks = 0, bool flip_heads = false)
 {
     // score_ks > 0 (hm_lowres forms only): scored_off, the offset taps refined from the stride-4 heat maps = hmps_hr itself
     OG_REQUIRE(score_ks == 0 || (score_ks >= 1 && score_ks <= 7 && score_ks % 2 == 1), OG_EINVAL,
@@ -1204,7 +1236,7 @@ static int generate_limbs_impl(const char *name, const float *hmps_hr, const flo
     const size_t topk = og_align_up(og_topk_workspace_bytes((long)N * C, H, W, k), 256);
     float *sc = own_lists ? reinterpret_cast<float *>(ws2 + topk + (size_t)N * C * k * 8) : topk_scores;
     int64_t *id = own_lists ? reinterpret_cast<int64_t *>(ws2 + topk) : topk_inds;
-    const Pairing pr{ca, vector_nd, N, score_ks > 0 ? hmps_hr : nullptr, score_ks, kp_perm};
+    const Pairing pr{ca, vector_nd, N, score_ks > 0 ? hmps_hr : nullptr, score_ks, kp_perm, flip_heads};
     const bool can_pair = (long)H * W < (1l << 31) && k <= 2048;
     OG_REQUIRE(!hm_lowres || (H % 4 == 0 && W % 4 == 0), OG_EINVAL, "%s: H,W must be multiples of 4", name);
     const int rc = hm_lowres ? run_topk<true, true>(hmps_hr, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
@@ -1313,6 +1345,30 @@ OG_API int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, cons
     return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, nullptr, 0, nullptr, 0, N, C, 4 * h, 4 * w, jf, jt, L, k, thre_hmp,
                                min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace,
                                workspace_bytes, stream, true, kp_perm, ksize);
+}
+
+// ---- the flip form with the optional heads: the scale pair (2N,C,h,w) and / or the jitter pair (2N,2,h,w) of [images | mirrored
+// images] sampled at the peaks as og_flip_merge_heads_f32 would have merged them (og_collect::FlipHeadsArgs); ksize 0 = unrefined
+// offsets, odd 1..7 = scored_off.  Bit-identical to og_flip_merge_f32 + og_flip_merge_heads_f32 + og_generate_limbs_fused[_scored]_f32.
+OG_API int og_generate_limbs_fused_flip_heads_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
+                                                  const int32_t *limb_perm, const int32_t *reserve_mask, int ksize,
+                                                  const float *scales_pair_lr, int scales_mode, const float *jitter_pair_lr,
+                                                  int jitter_mode, int N, int C, int h, int w, const int32_t *jf, const int32_t *jt,
+                                                  int L, int k, float thre_hmp, float min_len, float resize_factor, float *topk_scores,
+                                                  int64_t *topk_inds, float *limbs, void *workspace, size_t workspace_bytes,
+                                                  void *stream)
+{
+    const char *name = "og_generate_limbs_fused_flip_heads_f32";
+    OG_REQUIRE(ksize == 0 || (ksize >= 1 && ksize <= 7 && ksize % 2 == 1), OG_EINVAL, "%s: ksize must be 0 or odd, 1..7 (got %d)", name,
+               ksize);
+    OG_REQUIRE(kp_perm && limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
+    OG_REQUIRE(scales_pair_lr || jitter_pair_lr, OG_EINVAL, "%s: null pointer (neither head given: og_generate_limbs_fused_flip_f32)", name);
+    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
+    OG_REQUIRE(scales_mode == 0 || scales_mode >= 2, OG_EINVAL, "%s: the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
+    OG_REQUIRE(jitter_mode == 0 || jitter_mode == 3, OG_EINVAL, "%s: the jitter maps are the stride-4 head output (jitter_mode 3)", name);
+    return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, scales_pair_lr, scales_mode, jitter_pair_lr, jitter_mode, N, C, 4 * h,
+                               4 * w, jf, jt, L, k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm,
+                               reserve_mask, workspace, workspace_bytes, stream, true, kp_perm, ksize, true);
 }
 
 #ifdef OG_K1_STAMPS

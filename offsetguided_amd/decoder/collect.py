@@ -91,18 +91,30 @@ class LimbsCollect(object):
                 float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
         return limbs
 
-    def generate_limbs_fused_flip(self, hm_pair_lr, offs_pair_lr, kp_perm, limb_perm, reserve_mask, scored_ks=0):
+    def generate_limbs_fused_flip(self, hm_pair_lr, offs_pair_lr, kp_perm, limb_perm, reserve_mask, scored_ks=0, scmps_pair_lr=None,
+                                  scale_inter='bicubic', jomps_pair_lr=None):
         """generate_limbs_fused on the flip-merged maps WITHOUT merging them first (og_generate_limbs_fused_flip_f32): the stride-4
         head outputs of [images | mirrored images], (2N, C, h, w) and (2N, 2L, h, w); every heat-map source value and every offset tap
-        is computed as PostProcess.flip_augment would have written it (decoder/factory.py:98-146).  2-component offsets, no scale /
-        jitter head.  scored_ks > 0: scored_off with that window, every offset tap refined inside the pairing
-        (og_generate_limbs_fused_flip_scored_f32); 0 = the unrefined call."""
+        is computed as PostProcess.flip_augment would have written it (decoder/factory.py:98-146).  2-component offsets.  scored_ks > 0:
+        scored_off with that window, every offset tap refined inside the pairing (og_generate_limbs_fused_flip_scored_f32); 0 = the
+        unrefined call.  scmps_pair_lr (2N, C, h, w) / jomps_pair_lr (2N, 2, h, w): the keypoint-scale / jitter head outputs of the
+        same pairs, sampled at the peaks as flip_augment would have merged them (og_generate_limbs_fused_flip_heads_f32; the
+        jitter maps act under the conditions of _jitter and need square inputs, as everywhere)."""
         hm = _lib.require_device(hm_pair_lr, 'hmps')
         offs = _lib.require_device(offs_pair_lr, 'offs')
         n2, c, h, w = hm.shape
         n, n_limbs = n2 // 2, len(self.skeleton)
         assert n2 == 2 * n and tuple(offs.shape) == (n2, 2 * n_limbs, h, w), 'head outputs of [images | mirrored images] at stride 4'
         dev, lib = hm.device, _lib.load()
+        scl = jit = None
+        if scmps_pair_lr is not None:
+            scl = _lib.require_device(scmps_pair_lr, 'scmps')
+            assert tuple(scl.shape) == (n2, c, h, w), f'scale maps {tuple(scl.shape)}, expected {(n2, c, h, w)}'
+        if self._jitter(jomps_pair_lr) is not None:
+            jit = _lib.require_device(jomps_pair_lr, 'jomps')
+            assert tuple(jit.shape) == (n2, 2, h, w), f'jitter maps {tuple(jit.shape)}, expected {(n2, 2, h, w)}'
+            if h != w:   # the reference indexes the refinement maps [x][y] (collect.py:158-165)
+                raise NotImplementedError('the jitter-offset head needs square inputs (the reference indexes its maps [x][y])')
         limbs = torch.empty((n, n_limbs, self.K, 13), dtype=torch.float32, device=dev)
         jf, jt = _lib.int_table(self.jtypes_f, dev), _lib.int_table(self.jtypes_t, dev)
         with _lib.stage_timer('k1f_fused_limbs', dev):
@@ -111,7 +123,11 @@ class LimbsCollect(object):
                       _lib.ptr(_lib.int_table(reserve_mask, dev)))
             rest = (n, c, h, w, _lib.ptr(jf), _lib.ptr(jt), n_limbs, self.K, float(self.thre_hmp), float(self.min_len),
                     float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-            if scored_ks:
+            if scl is not None or jit is not None:
+                heads = (_lib.ptr(scl) if scl is not None else None, (2 if scale_inter == 'bicubic' else 3) if scl is not None else 0,
+                         _lib.ptr(jit) if jit is not None else None, 3 if jit is not None else 0)
+                _lib.check(lib.og_generate_limbs_fused_flip_heads_f32(*tables, int(scored_ks), *heads, *rest), lib)
+            elif scored_ks:
                 _lib.check(lib.og_generate_limbs_fused_flip_scored_f32(*tables, int(scored_ks), *rest), lib)
             else:
                 _lib.check(lib.og_generate_limbs_fused_flip_f32(*tables, *rest), lib)

@@ -139,8 +139,9 @@ class PostProcess(torch.nn.Module):
         # False / OG_FUSED_UPSAMPLE=0: K1a materialises the hi-res heatmaps and K1 streams them -- the reference's structure and the
         # HBM-roofline benchmark mode.
         self.fused_upsample = os.environ.get('OG_FUSED_UPSAMPLE', '1') != '0'
-        # flip-test (2-component offsets, no scale / jitter head): flip_augment's merge rides on the loads of K1a and on the
-        # offset sampling of K1 instead of running as its own pass (K0, og_flip_merge_f32); identical results
+        # flip-test (2-component offsets): flip_augment's merge rides on the loads of K1a and on the offset sampling of K1 instead of
+        # running as its own pass (K0, og_flip_merge_f32); identical results.  With K1-fused the keypoint-scale / jitter heads are
+        # sampled from their pairs the same way (og_generate_limbs_fused_flip_heads_f32)
         self.fold_flip = os.environ.get('OG_FOLD_FLIP', '1') != '0'
         # scored_off: the window of the heatmap-weighted offset refinement (the reference hard-codes 3 at its call site,
         # decoder/factory.py:70-72).  K1-fused refines every offset tap inside the pairing; fused_upsample=False runs
@@ -219,14 +220,21 @@ class PostProcess(torch.nn.Module):
                 _lib.ptr(_lib.int_table(keep, dev)), _lib.ptr(hm_out), _lib.ptr(off_out), _lib.stream_ptr(dev)), lib)
         if cat_flip_offs:
             off_out = off_out.view(n2, -1, h, w)  # the reference's (odd) shape of the same memory, factory.py:127
-        if self.include_jitter_offset and isinstance(jomps, torch.Tensor):  # factory.py:108-113, same ops (exact)
-            jomps = _lib.require_device(jomps, 'jomps')
-            flipped = torch.flip(jomps[n:], [-1])
-            flipped[:, ::2] *= -1
-            jomps = (jomps[:n] + flipped) / 2
-        if self.include_scale and isinstance(scmps, torch.Tensor):  # factory.py:141-144, same ops (exact)
-            scmps = _lib.require_device(scmps, 'scmps')
-            scmps = (scmps[:n] + torch.flip(scmps[n:], [-1])[:, self.keypoints_flips]) / 2
+        # factory.py:108-113 (jitter: mirror, negate x, average) and :141-144 (scale: mirror, permute, average): one launch for both
+        jit_in = _lib.require_device(jomps, 'jomps') if self.include_jitter_offset and isinstance(jomps, torch.Tensor) else None
+        scl_in = _lib.require_device(scmps, 'scmps') if self.include_scale and isinstance(scmps, torch.Tensor) else None
+        if jit_in is not None or scl_in is not None:
+            if jit_in is not None:
+                assert tuple(jit_in.shape) == (n2, 2, h, w), f'jitter maps {tuple(jit_in.shape)}, expected {(n2, 2, h, w)}'
+                jomps = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            if scl_in is not None:
+                assert tuple(scl_in.shape) == (n2, c, h, w), f'scale maps {tuple(scl_in.shape)}, expected {(n2, c, h, w)}'
+                scmps = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+            with _lib.stage_timer('k0_flip_merge_heads', dev):
+                _lib.check(lib.og_flip_merge_heads_f32(
+                    _lib.ptr(scl_in) if scl_in is not None else None, _lib.ptr(jit_in) if jit_in is not None else None, n, c, h, w,
+                    _lib.ptr(_lib.int_table(self.keypoints_flips, dev)), _lib.ptr(scmps) if scl_in is not None else None,
+                    _lib.ptr(jomps) if jit_in is not None else None, _lib.stream_ptr(dev)), lib)
         return hm_out, jomps, off_out, scmps, vector_nd
 
     # ---- device-resident pieces ----------------------------------------------------------
@@ -241,15 +249,18 @@ class PostProcess(torch.nn.Module):
         vector_nd = 2
         scored_ks = self.scored_kernel_size if scored_off else 0
         # (scored_off without K1-fused takes the unfolded route: the roofline-mode forms have no refined variant)
+        scl_pair = scmps if self.include_scale and isinstance(scmps, torch.Tensor) else None
+        jit_pair = jomps if self.include_jitter_offset and isinstance(jomps, torch.Tensor) else None
+        has_heads = scl_pair is not None or jit_pair is not None     # (the roofline-mode form has no heads variant: unfolded route)
         if (flip_test and self.fold_flip and not cat_flip_offs and not (scored_off and not self.fused_upsample)
-                and self.inter_mode == 'bicubic' and not (self.include_scale and isinstance(scmps, torch.Tensor))
-                and not (self.include_jitter_offset and isinstance(jomps, torch.Tensor))):
+                and self.inter_mode == 'bicubic' and not (has_heads and not self.fused_upsample)):
             n_limbs = offs.shape[1] // 2
             keep = [1 if l in self.limbs_flips[1] else 0 for l in range(n_limbs)]
             if self.fused_upsample:
                 try:
                     return self.limb_collect.generate_limbs_fused_flip(hmps, offs, self.keypoints_flips, self.limbs_flips[0], keep,
-                                                                       scored_ks=scored_ks)
+                                                                       scored_ks=scored_ks, scmps_pair_lr=scl_pair,
+                                                                       scale_inter=self.inter_mode, jomps_pair_lr=jit_pair)
                 except _lib.OgError as e:
                     # merge + pairing of the folded form keeps a plane's lists in LDS: beyond k ~ 226 at 640 x 640 (half that for inputs
                     # twice as tall) it does not fit and the C side says OG_EUNSUPPORTED.  The unfolded route below (flip_augment as its own

@@ -18,10 +18,17 @@ def _planes(t):
 def hmp_NMS(heat, kernel=3):
     """Keep kernel x kernel local maxima (zero padding), zero the rest: heat * (maxpool(heat) == heat).
 
-    kernel = 3 (the decoder's window, decoder/heatmap.py:15) is the hand-written HIP kernel; any other odd window runs the
-    reference's own three device ops (pad, max_pool2d, multiply: exact comparisons, so the result is the reference's bit for
-    bit); an even window fails as it does there (the padded pool no longer returns the input's size)."""
+    kernel = 3 (the decoder's window, decoder/heatmap.py:15) is the band kernel og_hmp_nms_f32, 5 and 7 the LDS-tiled
+    og_hmp_nms_k_f32 (exact compares, the reference's result bit for bit, signed zeros included); a larger odd window runs the
+    reference's own three device ops (pad, max_pool2d, multiply); an even window fails as it does there (the padded pool no
+    longer returns the input's size)."""
     heat = _lib.require_device(heat, "hmp_NMS(heat)")
+    if kernel in (5, 7):
+        lib = _lib.load()
+        planes, h, w = _planes(heat)
+        out = torch.empty_like(heat)
+        _lib.check(lib.og_hmp_nms_k_f32(_lib.ptr(heat), planes, h, w, int(kernel), _lib.ptr(out), _lib.stream_ptr(heat.device)), lib)
+        return out
     if kernel != 3:
         import torch.nn.functional as F
         pad = (kernel - 1) // 2

@@ -247,7 +247,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
 
     # multi-scale test (--test-scales with more than one scale; decoder/multiscale.py): per batch and scale the input chain
     # (EvalPreprocess.multi_scale: one H2D copy, one launch per scale), the engine of that scale's shape, then one og_scale_accumulate_f32
-    # launch per scale into the lane's base-grid accumulators and one submit of the averaged maps.  [1.0] runs the code above unchanged.
+    # launch per scale (og_scale_accumulate_heads_f32 with a keypoint-scale / jitter head) into the lane's base-grid accumulators and
+    # one submit of the averaged maps.  [1.0] runs the code above unchanged.
     scored_off = bool(getattr(args, 'scored_off', False))
     scales = validate_test_scales(getattr(args, 'test_scales', [1.0]), getattr(args, 'fixed_height', False),
                                   getattr(args, 'cat_flip_offset', False))
@@ -293,9 +294,12 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
         proc = processors[lane]
         inv = float(np.float32(1.0) / np.float32(len(scales)))
         with torch.cuda.stream(lanes[lane]):
+            has_scl, has_jit = slots[0][0].scale is not None, slots[0][0].jitter is not None   # forward_raw: (hm, off[, scale][, jitter])
             if accumulators[lane] is None or tuple(accumulators[lane][0].shape[2:]) != base_hw:
-                accumulators[lane] = (torch.empty((full_batch, len(proc.keypoints)) + base_hw, dtype=torch.float32, device=dev),
-                                      torch.empty((full_batch, 2 * len(proc.skeleton)) + base_hw, dtype=torch.float32, device=dev))
+                new = lambda ch: torch.empty((full_batch, ch) + base_hw, dtype=torch.float32, device=dev)  # noqa: E731
+                accumulators[lane] = (new(len(proc.keypoints)), new(2 * len(proc.skeleton)))
+                if has_scl or has_jit:
+                    accumulators[lane] += (new(len(proc.keypoints)) if has_scl else None, new(2) if has_jit else None)
             for slot in slots:
                 if slot[2] is not None:
                     lanes[lane].wait_event(slot[2])      # the engine's last batch (maybe on another lane): its merge has read the outputs
@@ -303,17 +307,15 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 # scale by scale: forward, then its merge, then the engine's event -- two scales of one padded size may share an engine,
                 # whose graph outputs the second forward overwrites (stream order: after the first merge has read them)
                 hm, off, *rest = slot[0].forward_raw(x)
-                if rest:
-                    raise NotImplementedError('multi-scale test merges the heatmap and offset heads only (no keypoint-scale / jitter head)')
+                scl = rest.pop(0) if has_scl else None
+                jit = rest.pop(0) if has_jit else None
                 mode = multiscale.MODE_WRITE if s == 0 else (multiscale.MODE_ADD_SCALE if s == len(inputs) - 1 else multiscale.MODE_ADD)
                 multiscale.accumulate_scale(hm, off, aff_dev[s], accumulators[lane], mode, inv, args.flip_test, proc.keypoints,
-                                            proc.skeleton)
+                                            proc.skeleton, scl, jit)
                 slot[2] = torch.cuda.Event()
                 slot[2].record(lanes[lane])
             # the accumulators are read by K1 on this lane before the lane's next batch writes them (stream order)
-            empty = [[] for _ in range(slot[0].n_stacks)]
-            feats = [([accumulators[lane][0]] * len(empty), list(empty), list(empty)),
-                     ([accumulators[lane][1]] * len(empty), list(empty), list(empty))]
+            feats = multiscale.merged_features(accumulators[lane], slot[0].n_stacks)
             return (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas)
 
     try:
