@@ -500,6 +500,24 @@ int og_focal_l2_loss_f32(const float *pred, const float *gt, const unsigned char
                          float tau, float gamma, float *sum, float *grad, void *stream);
 int og_offset_l1_loss_f32(const float *pred, const float *gt, const float *gt_ps, const unsigned char *mask_miss, int N,
                           int C, long hw, float margin, int sqrt_re, float *sum_count, float *grad, void *stream);
+/* The remaining loss choices and the optional heads (LossChoice :61-137), same conventions: caller-zeroed accumulators,
+ * gradient of the SUM written in the same pass, 0 for every dropped element (unlabelled, non-finite target, below margin).
+ * 16-byte accesses when hw % 4 == 0 and the pointers are 16-byte aligned, else 4-byte.
+ * og_l2_loss_f32: *sum += sum of 0.5 (p-g)^2 over labelled elements with finite gt; grad = p-g.
+ * og_masked_l1_loss_f32: e = |p-g| over labelled elements with finite gt (keypoint scales: NaN outside the patches; jitter
+ *   offsets: inf), kept if e >= margin (sqrt(e) if sqrt_re); sum_count[0] += sum, sum_count[1] += count.
+ * og_vector_l1_loss_f32: channels (2l, 2l+1) of pred/gt (N,C,hw), C even, are one vector: r = sqrt(dx^2 + dy^2), kept where
+ *   labelled, r finite and r >= margin (sqrt(r) if sqrt_re); grad = d/r per component (x 0.5/sqrt(r)).
+ * og_laplace_loss_f32: r as above, v = logb + r exp(-logb) with logb (N,C/2,hw) (the spread head), kept where labelled, r
+ *   finite and v >= margin (sqrt(v) if sqrt_re); grad (N,C,hw) = d sum / d pred, grad_logb (N,C/2,hw) = d sum / d logb. */
+int og_l2_loss_f32(const float *pred, const float *gt, const unsigned char *mask_miss, int N, int C, long hw, float *sum,
+                   float *grad, void *stream);
+int og_masked_l1_loss_f32(const float *pred, const float *gt, const unsigned char *mask_miss, int N, int C, long hw,
+                          float margin, int sqrt_re, float *sum_count, float *grad, void *stream);
+int og_vector_l1_loss_f32(const float *pred, const float *gt, const unsigned char *mask_miss, int N, int C, long hw,
+                          float margin, int sqrt_re, float *sum_count, float *grad, void *stream);
+int og_laplace_loss_f32(const float *pred, const float *gt, const float *logb, const unsigned char *mask_miss, int N, int C,
+                        long hw, float margin, int sqrt_re, float *sum_count, float *grad, float *grad_logb, void *stream);
 
 /* ---- ground-truth encoder ----
  * joints (N,P,n_kp,4) fp32 rows [x, y, v, scale] in input-image pixels (transforms/annotations.py:46-50), P = padded

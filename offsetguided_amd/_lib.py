@@ -91,6 +91,10 @@ SIGNATURES = {
     "og_encode_offsets_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "og_focal_l2_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _f, _vp, _vp, _vp]),
     "og_offset_l1_loss_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
+    "og_l2_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp]),
+    "og_masked_l1_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
+    "og_vector_l1_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
+    "og_laplace_loss_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -52,9 +52,11 @@ def train_cli(argv=None):
     return p.parse_args(argv)
 
 
-def synthetic_targets(seed, batch, size, device):
+def synthetic_targets(seed, batch, size, device, *, background=False, jitter=False, scale=False):
     """Encoder-style training targets (encoder/heatmap.py, encoder/offset.py conventions) for one batch:
-    annos = [(gt_hmp, gt_bghmp, gt_jomp, mask_miss), (gt_off, gt_scale, gt_ps, mask_miss)]."""
+    annos = [(gt_hmp, gt_bghmp, gt_jomp, mask_miss), (gt_off, gt_scale, gt_ps, mask_miss)].  The optional maps are None
+    unless asked for: background = 1 - max over the keypoint channels; jitter (N,2,h,w) sub-cell offsets round the peaks,
+    inf elsewhere; scale (N,17,h,w) keypoint scales round each channel's peaks, NaN elsewhere."""
     hm, off = synth.synth_batch(seed, batch, size, size, hm_noise=0.0, off_noise=0.0)
     off = np.where(off == 0.0, np.inf, off).astype(np.float32)          # offsets exist in the patches only
     h = size // 4
@@ -62,7 +64,17 @@ def synthetic_targets(seed, batch, size, device):
     ps = rng.uniform(batch * h * h, 40.0, 300.0).reshape(batch, 1, h, h).astype(np.float32)
     mask = torch.ones(batch, 1, h, h, dtype=torch.bool, device=device)
     t = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-    return [(t(np.clip(hm, 0, 1)), None, None, mask), (t(off), None, t(ps), mask)]
+    hm = np.clip(hm, 0, 1).astype(np.float32)
+    bg = jit = sc = None
+    if background:
+        bg = t(1.0 - hm.max(axis=1, keepdims=True))
+    if jitter:
+        jit = rng.uniform(batch * 2 * h * h, -0.5, 0.5).reshape(batch, 2, h, h).astype(np.float32)
+        jit = t(np.where(hm.max(axis=1, keepdims=True) >= 0.25, jit, np.float32(np.inf)))
+    if scale:
+        sc = rng.uniform(batch * hm.shape[1] * h * h, 1.0, 12.0).reshape(hm.shape).astype(np.float32)
+        sc = t(np.where(hm >= 0.25, sc, np.float32(np.nan)))
+    return [(t(hm), bg, jit, mask), (t(off), sc, t(ps), mask)]
 
 
 def synthetic_annotations(seed, batch, size):
@@ -83,9 +95,9 @@ def synthetic_annotations(seed, batch, size):
 def encode_targets(encoders, joints, n_persons):
     """Device-side ground truth (offsetguided_amd.encoder = reference encoder/): the same annos layout as
     synthetic_targets, produced from annotations by the HIP encoder kernels inside the step."""
-    hm, bg, _, mask = encoders[0].encode_batch(joints, n_persons)
+    hm, bg, jit, mask = encoders[0].encode_batch(joints, n_persons)
     off, sc, ps, _ = encoders[1].encode_batch(joints, n_persons)
-    return [(hm, bg if bg.numel() else None, None, mask), (off, sc if sc.numel() else None, ps, mask)]
+    return [(hm, bg if bg.numel() else None, jit if jit.numel() else None, mask), (off, sc if sc.numel() else None, ps, mask)]
 
 
 def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dtype=torch.bfloat16):
@@ -105,6 +117,21 @@ def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dty
     loss.backward()
     optimizer.step()
     return loss.detach(), [float(l.detach()) if torch.is_tensor(l) else float(l) for l in multi_losses]
+
+
+def describe_losses(args):
+    """The heads and loss choices of a run, for the --bench line: the default is 'focal-L2 hmp + L1 offset losses'."""
+    short = lambda name: {'focal_l2_loss': 'focal-L2', 'l2_loss': 'L2', 'offset_l1_loss': 'L1', 'vector_l1_loss': 'vector-L1',  # noqa: E731
+                          'offset_laplace_loss': 'laplace', 'offset_instance_l1_loss': 'instance-L1', 'scale_l1_loss': 'L1'}[name]
+    parts = [f'{short(args.hmp_loss)} hmp']
+    if args.include_background:
+        parts.append(f'{short(args.hmp_loss)} background')
+    if args.include_jitter_offset:
+        parts.append(f'{short(args.jitter_offset_loss)} jitter')
+    parts.append(f'{short(args.offset_loss)} offset' + (' (spread head)' if args.include_spread else ''))
+    if args.include_scale:
+        parts.append(f'{short(args.scale_loss)} scale')
+    return ' + '.join(parts) + ' losses' + (', sqrt' if args.sqrt_re else '') + ('' if args.fused_losses else ', torch-formulated')
 
 
 def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world):
@@ -162,7 +189,7 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
             'value': round(world * args.batch_size / step_s, 2), 'unit': 'images/sec', 'n_gpus': world,
             'steps': args.bench_steps, 'warmup': args.bench_warmup, 'ms_per_step': round(step_s * 1e3, 2),
             'config': {'workload': f'train_dist DDP, {args.square_length}x{args.square_length} crops, bs{args.batch_size}/GPU, '
-                                   'bf16 autocast, focal-L2 hmp + L1 offset losses (BASELINE configs[4])',
+                                   f'bf16 autocast, {describe_losses(args)} (BASELINE configs[4])',
                        'sync_bn': bool(args.sync_bn and world > 1), 'grad_payload': str(payload_dtype).replace('torch.', '')},
             'grad_allreduce': {'bytes': nbytes, 'ms': comm_ms, 'bus_GBps': bus,
                                'exposed_comm_ms': round(max(step_s - nosync_s, 0.0) * 1e3, 2) if world > 1 else 0.0},
@@ -219,9 +246,9 @@ def main(argv=None):
     # (the reference's numpy encoder manages 17 samples/s per dataloader worker, data/factory.py:284).
     pool, encoders = [], None
     if use_cuda:
-        encoder.HeatMaps.include_jitter_offset = False
-        encoder.HeatMaps.include_background = False
-        encoder.OffsetMaps.include_scale = False
+        encoder.HeatMaps.include_jitter_offset = args.include_jitter_offset
+        encoder.HeatMaps.include_background = args.include_background
+        encoder.OffsetMaps.include_scale = args.include_scale
         encoders = encoder.factory_heads(['hmp', 'omp'], args.square_length, [4, 4], dev)
     for i in range(4):
         imgs = torch.randn(args.batch_size, 3, args.square_length, args.square_length, device=dev)
@@ -230,7 +257,9 @@ def main(argv=None):
             joints, n_persons = synthetic_annotations(1000 * rank + i, args.batch_size, args.square_length)
             pool.append((imgs, (torch.from_numpy(joints).to(dev), torch.from_numpy(n_persons).to(dev))))
         else:
-            pool.append((imgs, synthetic_targets(1000 * rank + i, args.batch_size, args.square_length, dev)))
+            pool.append((imgs, synthetic_targets(1000 * rank + i, args.batch_size, args.square_length, dev,
+                                                 background=args.include_background, jitter=args.include_jitter_offset,
+                                                 scale=args.include_scale)))
     if args.bench:
         return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world)
     batch_time = AverageMeter()   # over the whole run: the first steps (MIOpen find, allocator warm-up) do not bias an epoch
