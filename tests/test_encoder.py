@@ -56,16 +56,16 @@ def test_encoder_factory_names():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES)
-def test_gpu_encoder_matches_reference_golden(case):
+def test_gpu_encoder_matches_reference_golden(case, monkeypatch):
     from offsetguided_amd import encoder
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected but no HIP device is visible")
     g = load()
     j, size = g[f"{case}_joints"], int(g[f"{case}_size"])
-    encoder.HeatMaps.include_jitter_offset = True
-    encoder.HeatMaps.include_background = True
-    encoder.OffsetMaps.include_scale = True
-    encoder.OffsetMaps.skeleton = cd.COCO_PERSON_SKELETON
+    monkeypatch.setattr(encoder.HeatMaps, "include_jitter_offset", True)      # class-level settings: they leave with the test
+    monkeypatch.setattr(encoder.HeatMaps, "include_background", True)
+    monkeypatch.setattr(encoder.OffsetMaps, "include_scale", True)
+    monkeypatch.setattr(encoder.OffsetMaps, "skeleton", cd.COCO_PERSON_SKELETON)
     hm_enc, off_enc = encoder.HeatMaps(size, 4), encoder.OffsetMaps(size, 4)
     # batch of 3: the case, the case with its persons reversed and padded (n_persons masks the padding), no person
     P = max(j.shape[0], 1) + 2
