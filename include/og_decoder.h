@@ -495,7 +495,9 @@ int og_conv2d_proj_f16(const void *x, const void *w_cat, const float *bias, cons
  *   gt (caller zeroes *sum); grad (N,C,hw) = d sum / d pred.
  * og_offset_l1_loss_f32: offset_instance_l1_loss :87-92 + OffsetMapsLoss :237-242.  e = |pred/ps - gt/ps| kept
  *   if e >= margin (sqrt(e) if sqrt_re); sum_count[0] += sum, sum_count[1] += count; grad = d sum / d pred
- *   (the caller scales by 1 / (1 + count)). */
+ *   (the caller scales by 1 / (1 + count)).
+ * All six loss entry points ADD to *sum / sum_count[0..1] with float atomics (one per wave) and never overwrite them: what the
+ *   caller left there stays in the result, and the count is a float. */
 int og_focal_l2_loss_f32(const float *pred, const float *gt, const unsigned char *mask_miss, int N, int C, long hw,
                          float tau, float gamma, float *sum, float *grad, void *stream);
 int og_offset_l1_loss_f32(const float *pred, const float *gt, const float *gt_ps, const unsigned char *mask_miss, int N,

@@ -41,7 +41,8 @@ focal_l2_kernel(const float *__restrict__ pred, const float *__restrict__ gt, co
             acc += 0.5f * d * d * f;
             // d|1-st|/ds = sign(om) * (fg ? -1 : +1)
             const float da = (om > 0.f ? 1.f : (om < 0.f ? -1.f : 0.f)) * (fg ? -1.f : 1.f);
-            const float df = (gamma == 1.f) ? da : gamma * powf(a, gamma - 1.f) * da;
+            // |x|^gamma at x = 0: derivative 0 (da = 0), also for gamma < 1 where powf(0, gamma - 1) = inf would make inf * 0 = NaN
+            const float df = (gamma == 1.f) ? da : (a > 0.f ? gamma * powf(a, gamma - 1.f) * da : 0.f);
             g = d * f + 0.5f * d * d * df;
         }
         grad[i] = g;
