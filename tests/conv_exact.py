@@ -1,0 +1,153 @@
+"""Exactly representable convolution operands and their unique expected output (tests/test_conv_exact_cpu.py,
+tests/test_gpu_conv_exact.py).
+
+Small integer activations and weights (half of them at the ends of their ranges), bias on the 2^-6 grid (odd numerators), residual / second input / `up` operands on the 2^-3 grid: every
+product, every partial sum in ANY order (MFMA accumulators, split-K slabs, LDS partial tiles), the bias add and the residual add are
+exact in fp32.  What is left is the one final rounding to the output type, which is round-to-nearest-even for a correct kernel
+(csrc/lp_dtype.h: f2lp) -- so the expected tensor is unique and the comparison is torch.equal, no tolerance.
+
+The reference is a plain fp64 sum over the k*k taps of a shifted NHWC slice times that tap's (Cin, Cout) matrix; it never calls
+torch's convolution (tests/test_conv_exact_cpu.py holds it to F.conv2d in fp64, bit for bit)."""
+import torch
+
+X_MAX, W_MAX = 3, 2                      # integer activations in [-3, 3], integer weights in [-2, 2]
+BIAS_GRID, BIAS_MAX = 64, 4              # bias = k / 64, k odd, |bias| <= 4 (fp32)
+RES_GRID, RES_MAX = 8, 8                 # residual / up = k / 8, |.| <= 8: exact in bf16 (8 significant bits) and fp16 alike
+SUM_LIMIT = 1 << 15
+MANTISSA_BITS = {torch.bfloat16: 8, torch.float16: 11}      # significant bits, the hidden one included
+
+
+def worst_case_sum(k_total):
+    """Largest |conv + bias + residual| for a reduction over k_total products: 6 K + 4 + 8."""
+    return X_MAX * W_MAX * k_total + BIAS_MAX + RES_MAX
+
+
+def check_precondition(k_total, bias_grid=BIAS_GRID):
+    """The bound that makes the exact test valid, from the shape alone: |sum| < 2^15 leaves at most 15 + 6 = 21 significant bits on the
+    2^-6 grid -- exact in fp32's 24, in any summation order -- and stays far below fp16's 65504.  (The largest K of the network,
+    9 * 512 + 512 = 5120, gives 30 732.)  A shape that breaks it is a mistake in the test: an error, never a skip."""
+    worst = worst_case_sum(k_total)
+    assert worst < SUM_LIMIT, f'K = {k_total}: worst-case |sum| {worst} >= 2^15, the operands are no longer exact in fp32'
+    # (a finer bias grid, tests/test_conv_exact_cpu.py: the same count of significant bits must still fit fp32's 24)
+    assert bias_grid >= RES_GRID and (worst * bias_grid).bit_length() <= 24, f'K = {k_total}, bias grid 1/{bias_grid}: more than 24 bits'
+    return worst
+
+
+def _ints(g, shape, lim):
+    """Integers in [-lim, lim]: half of the draws uniform over the range, half at its two ends.  The ranges are fixed; the weight on the
+    ends is what lets the sums of the small-K kernels (stem: K = 147, pointwise: K from 64) reach the magnitudes at which fp16, with
+    11 significant bits, rounds on the 2^-6 grid at all (|v| >= 32) -- the rounding-coverage condition of the tests."""
+    uniform = torch.randint(-lim, lim + 1, shape, generator=g).float()
+    ends = (torch.randint(0, 2, shape, generator=g).float() * 2 - 1) * lim
+    return torch.where(torch.rand(shape, generator=g) < 0.5, ends, uniform)
+
+
+def _grid(g, shape, grid, lim):
+    return torch.randint(-lim * grid, lim * grid + 1, shape, generator=g).float() / grid
+
+
+def _odd_grid(g, shape, grid, lim):
+    """k / grid with k odd, |k / grid| < lim: the lowest bit of the grid is set in every bias, hence in every sum that carries one."""
+    return (torch.randint(-lim * grid // 2, lim * grid // 2, shape, generator=g).float() * 2 + 1) / grid
+
+
+def exact_operands(seed, n, h, w, cin, cout, k=3, stride=1, second=None, up=False, bias_grid=BIAS_GRID):
+    """fp32 CPU tensors (NCHW) for one convolution case: x (n,cin,h,w), w (cout,cin,k,k), bias (cout,), res (n,cout,ho,wo) with
+    ho = (h + 2 (k // 2) - k) // stride + 1; with second = (h2, w2, cin2): x2 (n,cin2,h2,w2) and w2 (cout,cin2), the operand
+    concatenated along K (the residual's 1x1 projection, the junction's second input); with up: up (n,cout,2 ho,2 wo).
+    x2 lies on the 2^-3 grid like the residual but within the ACTIVATION range |x2| <= 3: the worst-case sum 6 K + 4 + 8 counts
+    every one of the K products, the second input's included, as at most 3 * 2.
+    bias_grid: 64 everywhere but in the sensitivity test (every k / 64 with |k| <= 256 has 8 significant bits and is exact in bf16
+    and fp16 alike; a bias that a 16-bit rounding would change needs a finer grid, and the precondition then counts its bits)."""
+    cin2 = second[2] if second is not None else 0
+    check_precondition(k * k * cin + cin2, bias_grid)
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    pad = k // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ops = {'x': _ints(g, (n, cin, h, w), X_MAX), 'w': _ints(g, (cout, cin, k, k), W_MAX),
+           'bias': _odd_grid(g, (cout,), bias_grid, BIAS_MAX), 'res': _grid(g, (n, cout, ho, wo), RES_GRID, RES_MAX)}
+    if second is not None:
+        h2, w2, _ = second
+        ops['x2'] = _grid(g, (n, cin2, h2, w2), RES_GRID, X_MAX)
+        ops['w2'] = _ints(g, (cout, cin2), W_MAX)
+    if up:
+        ops['up'] = _grid(g, (n, cout, 2 * ho, 2 * wo), RES_GRID, RES_MAX)
+    return ops
+
+
+def exact_sum(x, w, bias=None, res=None, relu=False, stride=1, x2=None, w2=None, stride2=1):
+    """act(conv(x, w) (+ conv1x1(x2, w2, stride2)) (+ bias) (+ res)) in fp64, NCHW, unrounded.  x (n,cin,h,w), w (cout,cin,k,k) with
+    pad k // 2; on the device of x."""
+    n, cin, h, wd = x.shape
+    cout, _, k, _ = w.shape
+    pad = k // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    xp = torch.zeros((n, h + 2 * pad, wd + 2 * pad, cin), dtype=torch.float64, device=x.device)
+    xp[:, pad:pad + h, pad:pad + wd] = x.permute(0, 2, 3, 1).double()
+    wt = w.double()
+    acc = torch.zeros((n, ho, wo, cout), dtype=torch.float64, device=x.device)
+    for ky in range(k):
+        for kx in range(k):
+            tap = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
+            acc += tap.reshape(-1, cin).matmul(wt[:, :, ky, kx].t()).view(n, ho, wo, cout)
+    if x2 is not None:
+        tap = x2.permute(0, 2, 3, 1).double()[:, 0:stride2 * (ho - 1) + 1:stride2, 0:stride2 * (wo - 1) + 1:stride2]
+        assert tuple(tap.shape[1:3]) == (ho, wo), 'the second input does not map onto the output'
+        acc += tap.reshape(-1, x2.shape[1]).matmul(w2.double().reshape(cout, -1).t()).view(n, ho, wo, cout)
+    return apply_epilogue(acc.permute(0, 3, 1, 2), bias, res, relu)
+
+
+def apply_epilogue(acc64, bias=None, res=None, relu=False):
+    """act(acc (+ bias) (+ res)) in fp64 on an NCHW accumulator (one exact_sum serves every epilogue combination of a case)."""
+    if bias is not None:
+        acc64 = acc64 + bias.double().view(1, -1, 1, 1)
+    if res is not None:
+        acc64 = acc64 + res.double()
+    return torch.relu(acc64) if relu else acc64
+
+
+def round_once(v64, dtype):
+    """The one rounding of a correct kernel: fp64 -> fp32 (exact under the precondition) -> RNE to the 16-bit type."""
+    assert torch.equal(v64.float().double(), v64), 'not exact in fp32: the precondition does not hold for these values'
+    return v64.float() if dtype == torch.float32 else v64.float().to(dtype)
+
+
+def exact_reference(x, w, bias=None, res=None, relu=False, stride=1, x2=None, w2=None, stride2=1, dtype=torch.bfloat16, up=None):
+    """The unique expected output.  dtype = the kernel's output type; torch.float32 (og_conv1x1_heads_*) = the exact value itself.
+    up: the contract of og_conv3x3_tiled_up2_* (include/og_decoder.h, models/hourglass_104.py:170-176) -- the convolution's result is
+    rounded to 16 bits, THEN added to `up` at nearest x2 and rounded again: round(up + nearest2x(round(act(conv + bias + skip))))."""
+    out = round_once(exact_sum(x, w, bias, res, relu, stride, x2, w2, stride2), dtype)
+    if up is not None:
+        low = out.double().repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+        out = round_once(up.double() + low, dtype)
+    return out
+
+
+def rounding_coverage(v64, dtype, expected=None):
+    """(elements whose expected value differs from the unrounded fp64 value v64, exact ties of the rounding of v64 to `dtype`,
+    elements).  expected: default the one rounding of v64; og_conv3x3_tiled_up2_* passes its twice-rounded expectation next to the
+    never-rounded up + nearest2x(act(conv + bias + skip))."""
+    r = (v64.float().to(dtype) if expected is None else expected).double()
+    changed = int((r != v64).sum())
+    m, _ = torch.frexp(v64.abs())                                   # |v| = m 2^e, m in [0.5, 1)
+    scaled = m * float(1 << MANTISSA_BITS[dtype])
+    ties = int(((scaled - scaled.floor()) == 0.5).sum())            # exactly half a unit in the last place: RNE decides
+    return changed, ties, v64.numel()
+
+
+def describe_mismatch(got, exp):
+    """Assert message for torch.equal(got, exp) on (n, c, y, x) tensors: how many differ, the first one, border or interior, and the
+    coordinates modulo 16 (tile and K-split seams show up as a pattern there).  '' when the tensors are equal."""
+    if got.shape != exp.shape:
+        return f'shape {tuple(got.shape)} != expected {tuple(exp.shape)}'
+    g, e = got.float(), exp.float()
+    bad = (g != e) | (g.isnan() != e.isnan())
+    bad &= ~(g.isnan() & e.isnan())
+    count = int(bad.sum())
+    if count == 0:
+        return ''
+    n, c, y, x = (int(i) for i in bad.nonzero()[0])
+    _, _, h, w = got.shape
+    where = 'border' if y in (0, h - 1) or x in (0, w - 1) else 'interior'
+    return (f'{count} of {bad.numel()} elements differ; first at (n={n}, c={c}, y={y}, x={x}): got {g[n, c, y, x].item()!r}, expected '
+            f'{e[n, c, y, x].item()!r}; {where} pixel of {h}x{w}; y % 16 = {y % 16}, x % 16 = {x % 16}, c % 16 = {c % 16}')

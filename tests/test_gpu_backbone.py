@@ -58,8 +58,11 @@ def test_upsample2_add_matches_torch(dev):
     assert torch.equal(up, ref)
 
 
-@pytest.mark.parametrize("shape", [(8, 5, 5, 512, 512), (8, 10, 10, 384, 384), (2, 20, 20, 384, 384), (3, 7, 9, 64, 128),
-                                   (1, 1, 1, 128, 64), (8, 20, 20, 384, 384), (2, 33, 31, 128, 256)])
+CONV3X3_SHAPES = [(8, 5, 5, 512, 512), (8, 10, 10, 384, 384), (2, 20, 20, 384, 384), (3, 7, 9, 64, 128),
+                                   (1, 1, 1, 128, 64), (8, 20, 20, 384, 384), (2, 33, 31, 128, 256)]
+
+
+@pytest.mark.parametrize("shape", CONV3X3_SHAPES)
 def test_conv3x3_matches_torch(dev, shape):
     """og_conv3x3_bf16 (split-K MFMA kernel, last-arriver reduction inside the launch, fused epilogue) vs an fp32 torch
     convolution of the same bf16 operands: differences are the final bf16 rounding (2^-9 relative) plus fp32 summation order."""
@@ -89,11 +92,14 @@ def test_conv3x3_matches_torch(dev, shape):
     assert ws[:256].count_nonzero().item() == 0              # the zero page is never written
 
 
-@pytest.mark.parametrize("shape", [(2, 20, 20, 384, 384, 3, 2), (2, 20, 20, 384, 384, 1, 2), (8, 5, 5, 512, 384, 1, 1),
+CONV2D_SHAPES = [(2, 20, 20, 384, 384, 3, 2), (2, 20, 20, 384, 384, 1, 2), (8, 5, 5, 512, 384, 1, 1),
                                    (8, 10, 10, 384, 512, 3, 2), (8, 10, 10, 384, 512, 1, 2), (3, 7, 9, 64, 128, 3, 2),
                                    (3, 7, 9, 128, 64, 1, 2), (1, 1, 1, 128, 64, 1, 1), (2, 64, 64, 128, 256, 3, 2),
                                    (2, 64, 64, 128, 256, 1, 2), (2, 80, 80, 256, 256, 1, 1), (2, 33, 31, 128, 256, 3, 1),
-                                   (1, 96, 96, 256, 384, 3, 2), (4, 160, 160, 256, 64, 1, 1)])
+                                   (1, 96, 96, 256, 384, 3, 2), (4, 160, 160, 256, 64, 1, 1)]
+
+
+@pytest.mark.parametrize("shape", CONV2D_SHAPES)
 def test_conv2d_matches_torch(dev, shape):
     """og_conv2d_bf16 (1x1 / 3x3, stride 1 / 2, fused epilogue) vs an fp32 torch convolution of the same bf16 operands."""
     import torch.nn.functional as F
@@ -124,8 +130,11 @@ def test_conv2d_matches_torch(dev, shape):
     assert ws[:256].count_nonzero().item() == 0
 
 
-@pytest.mark.parametrize("shape", [(8, 5, 5, 384, 384, 512, 1), (8, 5, 5, 512, 512, 384, 2), (8, 10, 10, 384, 384, 384, 2),
-                                   (2, 20, 20, 384, 384, 384, 2), (3, 7, 9, 64, 128, 192, 1), (2, 9, 6, 128, 64, 64, 2)])
+CONV2D_PROJ_SHAPES = [(8, 5, 5, 384, 384, 512, 1), (8, 5, 5, 512, 512, 384, 2), (8, 10, 10, 384, 384, 384, 2),
+                                   (2, 20, 20, 384, 384, 384, 2), (3, 7, 9, 64, 128, 192, 1), (2, 9, 6, 128, 64, 64, 2)]
+
+
+@pytest.mark.parametrize("shape", CONV2D_PROJ_SHAPES)
 def test_conv2d_proj_matches_torch(dev, shape):
     """og_conv2d_proj_bf16 = relu(conv3x3(y) + conv1x1(x, stride) + bias), the tail of a projection residual
     (models/hourglass_104.py:70-79), vs fp32 torch convolutions of the same bf16 operands."""
@@ -172,11 +181,14 @@ def test_conv2d_rejects_bad_arguments(dev):
         assert lib.og_conv2d_workspace_bytes(1, 8, 8, 64, 64, k, st) == 0
 
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("shape", [(1, 16, 16, 64, 128), (2, 32, 32, 128, 128), (1, 48, 32, 192, 256), (2, 80, 80, 256, 256),
+CONV3X3_TILED_SHAPES = [(1, 16, 16, 64, 128), (2, 32, 32, 128, 128), (1, 48, 32, 192, 256), (2, 80, 80, 256, 256),
                                    (1, 4, 40, 64, 128), (2, 40, 40, 384, 384), (1, 12, 40, 128, 256), (3, 16, 32, 64, 384),
                                    (8, 40, 40, 384, 384), (8, 20, 20, 384, 384), (2, 20, 20, 256, 128), (8, 40, 40, 256, 256),
-                                   (1, 8, 20, 128, 256)])
+                                   (1, 8, 20, 128, 256)]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("shape", CONV3X3_TILED_SHAPES)
 def test_conv3x3_tiled_kernel_matches_torch(dev, shape, dtype):
     """og_conv3x3_tiled_* (csrc/conv3x3_tiled.inc: two 4-wave workgroups per CU, pre-tiled weights, 32-channel K steps) vs an
     fp32 torch convolution of the same 16-bit operands, with and without the residual / ReLU epilogue; bit-identical
@@ -212,10 +224,13 @@ def test_conv3x3_tiled_kernel_matches_torch(dev, shape, dtype):
         assert torch.equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("shape", [(1, 16, 32, 64, 128), (2, 32, 32, 128, 256), (1, 48, 64, 192, 128), (2, 160, 160, 256, 256),
+CONV3X3S2_TILED_SHAPES = [(1, 16, 32, 64, 128), (2, 32, 32, 128, 256), (1, 48, 64, 192, 128), (2, 160, 160, 256, 256),
                                    (1, 16, 96, 64, 384), (1, 320, 320, 128, 256), (1, 4, 80, 64, 128), (2, 80, 80, 256, 384),
-                                   (3, 12, 80, 128, 128)])
+                                   (3, 12, 80, 128, 128)]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("shape", CONV3X3S2_TILED_SHAPES)
 def test_conv3x3s2_tiled_kernel_matches_torch(dev, shape, dtype):
     """og_conv3x3s2_tiled_* (stride 2, pad 1: the four input-parity phase images of a 16 x 8 output tile gathered by LDS-DMA,
     weights pre-tiled in the order the phase groups consume them) vs an fp32 torch convolution of the same 16-bit operands;
@@ -253,9 +268,12 @@ def test_conv3x3s2_tiled_kernel_matches_torch(dev, shape, dtype):
     assert rc == _lib.OG_EUNSUPPORTED
 
 
+CONV1X1_TILED_CASES = [(2, 40, 40, 256, 256, 1, True), (1, 33, 21, 128, 128, 1, False), (2, 32, 48, 128, 256, 2, False),
+                                  (1, 160, 160, 256, 256, 1, True), (3, 20, 24, 384, 256, 1, False), (1, 64, 64, 64, 384, 2, False)]
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("case", [(2, 40, 40, 256, 256, 1, True), (1, 33, 21, 128, 128, 1, False), (2, 32, 48, 128, 256, 2, False),
-                                  (1, 160, 160, 256, 256, 1, True), (3, 20, 24, 384, 256, 1, False), (1, 64, 64, 64, 384, 2, False)])
+@pytest.mark.parametrize("case", CONV1X1_TILED_CASES)
 def test_conv1x1_tiled_matches_torch(dev, case, dtype):
     """og_conv1x1_tiled_* vs fp32 torch: one input (stride 1 / 2: the projection `skip` of the residuals, raw and with bias +
     residual + ReLU) and two inputs concatenated along K (the inters_ / cnvs_ junction); tile tails (M not a multiple of 256)."""
@@ -296,8 +314,11 @@ def test_conv1x1_tiled_matches_torch(dev, case, dtype):
     assert rc == _lib.OG_EUNSUPPORTED
 
 
+CONV1X1_HEADS_CASES = [(2, 40, 40, 256, (17, 38)), (1, 33, 21, 128, (17, 38, 17)), (1, 160, 160, 256, (17, 38)), (2, 16, 16, 64, (17, 38, 17, 2))]
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("case", [(2, 40, 40, 256, (17, 38)), (1, 33, 21, 128, (17, 38, 17)), (1, 160, 160, 256, (17, 38)), (2, 16, 16, 64, (17, 38, 17, 2))])
+@pytest.mark.parametrize("case", CONV1X1_HEADS_CASES)
 def test_conv1x1_heads_matches_torch(dev, case, dtype):
     """og_conv1x1_heads_*: all heads as one 1x1 convolution, dense fp32 NCHW outputs per head with the bias added in fp32 (no
     16-bit rounding of the result: the error left is the fp32 summation order)."""
@@ -358,9 +379,12 @@ def test_conv3x3_tiled_repeated_full_size(dev):
     assert d <= 2 ** -6 * max(1.0, old.float().abs().max().item()), d     # same operands, different fp32 summation order
 
 
+CONV3X3_TILED_UP2_SHAPES = [(2, 32, 32, 128, 256), (1, 80, 80, 256, 256), (3, 40, 40, 384, 256), (2, 12, 40, 256, 384),
+                                   (8, 20, 20, 384, 384), (2, 16, 48, 64, 128)]
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("shape", [(2, 32, 32, 128, 256), (1, 80, 80, 256, 256), (3, 40, 40, 384, 256), (2, 12, 40, 256, 384),
-                                   (8, 20, 20, 384, 384), (2, 16, 48, 64, 128)])
+@pytest.mark.parametrize("shape", CONV3X3_TILED_UP2_SHAPES)
 def test_conv3x3_tiled_up2_equals_conv_then_upsample_add(dev, shape, dtype):
     """og_conv3x3_tiled_up2_* (the hourglass merge on the epilogue of the convolution below it, models/hourglass_104.py:170-176)
     == og_conv3x3_tiled_* followed by og_upsample2_add_*, bit for bit -- every tile shape, K-split shapes included, with and
@@ -461,7 +485,10 @@ def test_conv_band_rejects_bad_arguments(dev):
                                  _lib.stream_ptr(dev)) == -1
 
 
-@pytest.mark.parametrize("shape", [(1, 32, 32), (2, 64, 96), (1, 128, 64)])
+STEM_SHAPES = [(1, 32, 32), (2, 64, 96), (1, 128, 64)]
+
+
+@pytest.mark.parametrize("shape", STEM_SHAPES)
 def test_stem7x7_matches_torch(dev, shape):
     """og_stem7x7_bf16 (fp32 NCHW in, conv 7x7 s2 p3 + bias + ReLU, bf16 NHWC out) vs an fp32 torch convolution of the
     bf16-rounded operands."""
@@ -683,9 +710,12 @@ def test_run_images_synthetic(dev):
 
 
 # ---------------------------------------------------------------------------------- fp16 build of the backbone kernels
-@pytest.mark.parametrize("shape", [(8, 5, 5, 512, 512, 3, 1), (2, 20, 20, 384, 384, 3, 2), (2, 160, 160, 256, 256, 3, 1),
+CONV2D_F16_SHAPES = [(8, 5, 5, 512, 512, 3, 1), (2, 20, 20, 384, 384, 3, 2), (2, 160, 160, 256, 256, 3, 1),
                                    (2, 80, 80, 256, 256, 3, 1), (2, 40, 40, 384, 384, 3, 1), (3, 7, 9, 128, 64, 1, 2),
-                                   (2, 33, 31, 128, 256, 3, 1)])
+                                   (2, 33, 31, 128, 256, 3, 1)]
+
+
+@pytest.mark.parametrize("shape", CONV2D_F16_SHAPES)
 def test_conv2d_f16_matches_torch(dev, shape):
     """og_conv2d_f16 (the split-K kernel on small and large shapes, 1x1, stride 2) vs an fp32 torch convolution of the
     same fp16 operands: differences are the final fp16 rounding (2^-11 relative) plus fp32 summation order."""
