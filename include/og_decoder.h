@@ -540,6 +540,31 @@ int og_encode_offsets_f32(const float *joints, const int32_t *n_persons, int N, 
                           const int32_t *jt, int L, int in_w, int in_h, int stride, int fill_size, float min_jscale,
                           const float *sigmas, float *off, float *scale, float *pscale, void *stream);
 
+/* ---- pose painter (visualization/__init__.py:draw_poses, evaluate.py --show-detected-poses) ----
+ * Paints skeletons over images (N,H,W,3) uint8 RGB IN PLACE: what the reference's KeypointPainter.keypoints shows
+ * (visualization/show.py:225-253 -- one colour per person, limbs with round caps, a marker per visible keypoint, no box) as a
+ * capsule / disc rasteriser of this library's own, not matplotlib's renderer.  All pointers are device pointers:
+ * poses (N,P,K,3) fp32 rows x, y, v in pixel coordinates of `images`; n_persons int32[N], persons in use per image (clamped
+ * to [0, P]; the rows beyond are never read); skeleton int32 (L,2), ZERO-based keypoint indices (a limb with an index outside
+ * [0, K) is skipped); palette (n_colors,3) uint8.  No workspace.
+ * Primitives of image n, in this order: for person p = 0 .. n_persons[n]-1 the L limbs in skeleton order, then the K
+ * keypoints in index order.  A limb (a, b) is a capsule of radius r = line_width / 2 between the two keypoints, drawn only if
+ * both have v > 0 and all four coordinates are finite; a keypoint is a disc of radius r = marker_radius, drawn only if v > 0
+ * and its coordinates are finite.  Colour: palette[p % n_colors].  The centre of the pixel in column i, row j is (i, j).
+ * Coverage of a pixel centre (px, py): cov = clamp(r + 0.5 - d, 0, 1), d its distance to the segment / the disc centre, with
+ *   dx = bx - ax, dy = by - ay, len2 = dx*dx + dy*dy,
+ *   t = clamp(((px - ax)*dx + (py - ay)*dy) / len2, 0, 1), t = 0 when len2 == 0 (and for a disc),
+ *   qx = ax + t*dx, qy = ay + t*dy, d = sqrt((px - qx)*(px - qx) + (py - qy)*(py - qy)),
+ * every operation one IEEE fp32 operation, left to right as written, no contraction, correctly rounded divide and square
+ * root; clamp(x, 0, 1) = fmin(fmax(x, 0), 1).  A pixel keeps its three channels in fp32 and, for every primitive with cov > 0
+ * in primitive order, c = c + (colour - c) * (cov * alpha); a pixel no primitive covers is never written, a covered one is
+ * stored once as (uint8) floor(c + 0.5).  Blending does not commute: the order is part of the result.
+ * OG_EINVAL (nothing launched): a null pointer, a non-positive N, H, W, P, K or L, n_colors <= 0, alpha outside (0, 1], a
+ * negative or non-finite line_width / marker_radius, N or ceil(H / 8) beyond 65535. */
+int og_draw_poses_u8(void *images, const float *poses, const int *n_persons, const int *skeleton,
+                     const unsigned char *palette, int n_colors, int N, int H, int W, int P, int K, int L,
+                     float line_width, float marker_radius, float alpha, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

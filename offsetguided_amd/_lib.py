@@ -95,6 +95,7 @@ SIGNATURES = {
     "og_masked_l1_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
     "og_vector_l1_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
     "og_laplace_loss_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp, _vp]),
+    "og_draw_poses_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -56,7 +56,10 @@ def evaluate_cli(argv=None):
     parser.add_argument('--all-images', default=False, action='store_true')
     parser.add_argument('--resume', '-r', action='store_true', default=False, help='load --checkpoint-whole')
     parser.add_argument('--checkpoint-path', '-p', default='link2checkpoints_storage')
-    parser.add_argument('--show-detected-poses', action='store_true', default=False)
+    parser.add_argument('--show-detected-poses', action='store_true', default=False,
+                        help="paint every batch's poses over the network-input images on the device (visualization.draw_poses) and "
+                             'write the first image of each batch to <show-dir>/<dump-name>.poses.<batch>.ppm')
+    parser.add_argument('--show-dir', default='.', type=str, help='directory of the --show-detected-poses images')
     g = parser.add_argument_group('apex configuration (accepted for command-line compatibility, unused)')
     g.add_argument('--local_rank', default=0, type=int)
     g.add_argument('--opt-level', type=str, default='O2')
@@ -162,7 +165,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     """The hot loop of evaluate.py:207-298.  Returns (result_keypoints, result_image_ids).
     stats: an optional dict that receives `host_enqueue_s` (per batch: host time to queue the input chain, the forward and the decoder --
     no wait in it), `engines_built`, `torch_conv_calls` (0: every engine is strict, models/engine.py), `test_scales` and
-    `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it).
+    `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it) and, with args.show_detected_poses, `pose_images` (the files written).
     args.test_scales (--test-scales, default [1.0]): more than one scale runs the multi-scale test (enqueue_multi_scale below)."""
     if not torch.cuda.is_available():
         raise RuntimeError('run_images needs a HIP device (offsetguided_amd has no CPU path)')
@@ -188,9 +191,33 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     full_batch = None
     first_engine = [None]
 
+    # --show-detected-poses (evaluate.py:267-284): a batch's handle also carries (batch index, uint8 copy of the network-input batch);
+    # once its poses are on the host they are painted over that copy on the device, in network-input coordinates (before
+    # annotations_inverse), and the first image -- the reference shows batch_poses[0] -- is written as a PPM.  Off: nothing below runs
+    show = bool(getattr(args, 'show_detected_poses', False))
+    if show:
+        from . import visualization
+        show_dir = getattr(args, 'show_dir', '.')
+        os.makedirs(show_dir, exist_ok=True)
+
+    def canvas_of(images, normalised):
+        """(n, 3, H, W) network-input batch -> (n, H, W, 3) uint8 RGB: the pixels the input chain normalised, or, for a tensor batch
+        (synthetic_loader's random floats: no image behind it), a black canvas of the batch's size."""
+        if not normalised:
+            return torch.zeros((images.shape[0],) + tuple(images.shape[2:]) + (3,), dtype=torch.uint8, device=dev)
+        return visualization.denormalise_u8(images)
+
     def collect(handle):
-        poses, metas = handle
-        for image_poses, image_meta in zip(poses.result(), metas):   # zip drops the padded images of a ragged batch
+        poses, metas = handle[:2]
+        batch_poses = poses.result()
+        if len(handle) > 2:
+            batch_idx, canvas = handle[2]
+            visualization.draw_poses(canvas, list(batch_poses[:canvas.shape[0]]), processors[0].skeleton)
+            path = os.path.join(show_dir, f'{args.dump_name}.poses.{batch_idx}.ppm')
+            visualization.save_ppm(path, canvas[0])
+            if stats is not None:
+                stats.setdefault('pose_images', []).append(path)
+        for image_poses, image_meta in zip(batch_poses, metas):   # zip drops the padded images of a ragged batch
             poses_to_results(image_poses, image_meta, result_keypoints, result_image_ids)
 
     preprocess, packer = [None], [None]
@@ -271,6 +298,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
         cur = torch.cuda.current_stream(dev)
         inputs, tables = [], []
         base_hw = tuple(s_ // 4 for s_ in per_scale[base][0].shape[2:])
+        shown = ((batch_idx, canvas_of(per_scale[base][0], True)),) if show else ()     # the scale-1 batch is the one painted
         for x, metas_s in per_scale:
             aff = decoder.scale_affines(base_metas, metas_s, base_hw, tuple(s_ // 4 for s_ in x.shape[2:]))
             if n < full_batch:         # last batch of the dataset: filled up to the engine's batch, results are dropped
@@ -316,7 +344,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 slot[2].record(lanes[lane])
             # the accumulators are read by K1 on this lane before the lane's next batch writes them (stream order)
             feats = multiscale.merged_features(accumulators[lane], slot[0].n_stacks)
-            return (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas)
+            return (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas) + shown
 
     try:
         for batch_idx, ((images, _, metas), packed) in enumerate(ahead(data_loader)):
@@ -330,6 +358,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     # ToTensor + Normalize; pinned staging packed a batch ahead, one H2D copy); metas are derived here
                     images, metas = preprocess[0](images, image_ids=[m['image_id'] for m in metas], packed=packed.result())
                 images = feeder(images)
+                shown = ((batch_idx, canvas_of(images, packed is not None)),) if show else ()
                 full_batch = full_batch or images.shape[0]
                 if images.shape[0] < full_batch:   # last batch of the dataset: fill up to the engine's batch, results are dropped
                     images = torch.cat((images, images[-1:].expand(full_batch - images.shape[0], -1, -1, -1)))
@@ -346,7 +375,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 with torch.cuda.stream(lanes[lane]):
                     outputs = slot[0](images)
                     handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset,
-                                                      scored_off=scored_off), metas)
+                                                      scored_off=scored_off), metas) + shown
                     slot[1], slot[2] = batch_idx, torch.cuda.Event()
                     slot[2].record(lanes[lane])
             pending.append(handle)
