@@ -151,3 +151,58 @@ def describe_mismatch(got, exp):
     where = 'border' if y in (0, h - 1) or x in (0, w - 1) else 'interior'
     return (f'{count} of {bad.numel()} elements differ; first at (n={n}, c={c}, y={y}, x={x}): got {g[n, c, y, x].item()!r}, expected '
             f'{e[n, c, y, x].item()!r}; {where} pixel of {h}x{w}; y % 16 = {y % 16}, x % 16 = {x % 16}, c % 16 = {c % 16}')
+
+
+# ------------------------------------------------------------------------------------------- recording the engine's conv launches
+def record_key(name, a):
+    """(family, shape tuple as in CASES, epilogue) of one launch: the entry point and its integer arguments; pointers as present / null."""
+    has = lambda i: a[i] is not None        # noqa: E731
+    if name in ('og_conv3x3_tiled', 'og_conv3x3_tiled_up2', 'og_conv3x3s2_tiled', 'og_conv3x3'):
+        return name[3:], tuple(a[5:10]), (has(3), a[10])
+    if name == 'og_conv2d':
+        return 'conv2d', tuple(a[5:12]), (has(3), a[12])
+    if name == 'og_conv2d_proj':
+        assert (a[10], a[11]) == (3, 1)
+        return 'conv2d_proj', tuple(a[5:10]) + tuple(a[12:16]), (False, a[16])
+    if name == 'og_conv_band':
+        return 'conv_band', tuple(a[6:12]) + ((tuple(a[13:17]) if has(4) else None),), (has(3), a[12])
+    if name == 'og_conv1x1_tiled':
+        assert not has(5) or (a[6], a[7], a[8], a[9]) == (a[1], a[2], a[3], a[4])
+        assert (a[15], a[16]) == ((a[2] - 1) // a[4] + 1, (a[3] - 1) // a[4] + 1)
+        return 'conv1x1_tiled', (a[14], a[2], a[3], a[1], a[17], a[4], has(5)), (has(11), has(12), a[18])
+    if name == 'og_conv1x1_heads':
+        heads = tuple(a[9][i] for i in range(a[8]))
+        assert a[7] == (sum(heads) + 63) // 64 * 64
+        return 'conv1x1_heads', (a[4], a[5], a[6], a[1], heads), ()
+    if name == 'og_stem7x7':
+        return 'stem7x7', tuple(a[4:7]), (a[7],)
+    raise AssertionError(f'unknown conv entry point {name}')
+
+
+def record_launches(monkeypatch, on_launch, extra=()):
+    """Wrap every 16-bit conv / stem entry point of the loaded library so that each launch calls on_launch(record_key(...)) first,
+    and hold _lib.lp to handing out wrapped functions only (a conv launch that bypassed the recorder fails there).  extra: further
+    entry-point stems (both 16-bit twins) or full names, reported as (name, (), ()).  -> the number of conv entry points wrapped."""
+    from offsetguided_amd import _lib
+    lib = _lib.load()
+
+    def recording(name, fn, conv):
+        def call(*a):
+            on_launch(record_key(name, a) if conv else (name, (), ()))
+            return fn(*a)
+        call.records_conv_launch = True
+        return call
+    launches = [n for n in _lib.SIGNATURES if n.startswith(('og_conv', 'og_stem')) and n.endswith(('_bf16', '_f16'))]
+    for name in launches:
+        monkeypatch.setattr(lib, name, recording(name.rsplit('_', 1)[0], getattr(lib, name), True))
+    for stem in extra:
+        for name in ([stem] if stem in _lib.SIGNATURES else [stem + '_bf16', stem + '_f16']):
+            monkeypatch.setattr(lib, name, recording(stem, getattr(lib, name), False))
+    orig_lp = _lib.lp
+
+    def lp(lib_, stem, dtype):
+        fn = orig_lp(lib_, stem, dtype)
+        assert not stem.startswith(('og_conv', 'og_stem')) or getattr(fn, 'records_conv_launch', False), stem
+        return fn
+    monkeypatch.setattr(_lib, 'lp', lp)
+    return len(launches)

@@ -456,31 +456,6 @@ def test_rounding_is_exercised_in_every_family():
 
 
 # ---------------------------------------------------------------------------------------- the engine's launches are in the table
-def _record_key(name, a):
-    """(family, shape tuple as in CASES, epilogue) of one launch: the entry point and its integer arguments; pointers as present / null."""
-    has = lambda i: a[i] is not None        # noqa: E731
-    if name in ('og_conv3x3_tiled', 'og_conv3x3_tiled_up2', 'og_conv3x3s2_tiled', 'og_conv3x3'):
-        return name[3:], tuple(a[5:10]), (has(3), a[10])
-    if name == 'og_conv2d':
-        return 'conv2d', tuple(a[5:12]), (has(3), a[12])
-    if name == 'og_conv2d_proj':
-        assert (a[10], a[11]) == (3, 1)
-        return 'conv2d_proj', tuple(a[5:10]) + tuple(a[12:16]), (False, a[16])
-    if name == 'og_conv_band':
-        return 'conv_band', tuple(a[6:12]) + ((tuple(a[13:17]) if has(4) else None),), (has(3), a[12])
-    if name == 'og_conv1x1_tiled':
-        assert not has(5) or (a[6], a[7], a[8], a[9]) == (a[1], a[2], a[3], a[4])
-        assert (a[15], a[16]) == ((a[2] - 1) // a[4] + 1, (a[3] - 1) // a[4] + 1)
-        return 'conv1x1_tiled', (a[14], a[2], a[3], a[1], a[17], a[4], has(5)), (has(11), has(12), a[18])
-    if name == 'og_conv1x1_heads':
-        heads = tuple(a[9][i] for i in range(a[8]))
-        assert a[7] == (sum(heads) + 63) // 64 * 64
-        return 'conv1x1_heads', (a[4], a[5], a[6], a[1], heads), ()
-    if name == 'og_stem7x7':
-        return 'stem7x7', tuple(a[4:7]), (a[7],)
-    raise AssertionError(f'unknown conv entry point {name}')
-
-
 def _table_keys():
     keys = set()
     for family, shapes in CASES.items():
@@ -494,26 +469,8 @@ def _table_keys():
 def test_engine_launches_are_all_in_the_table(dev, shape, monkeypatch):
     """Every conv launch of the strict fp16 engine (use_graph=False, bench_init weights) at this input shape -- entry point, integer
     arguments, which optional operands are present -- is one of the cases this file runs exactly."""
-    lib = _lib.load()
     records = set()
-
-    def recording(name, fn):
-        def call(*a):
-            records.add(_record_key(name, a))
-            return fn(*a)
-        call.records_conv_launch = True
-        return call
-    launches = [n for n in _lib.SIGNATURES if n.startswith(('og_conv', 'og_stem')) and n.endswith(('_bf16', '_f16'))]
-    assert len(launches) == 2 * len(CASES)
-    for name in launches:
-        monkeypatch.setattr(lib, name, recording(name.rsplit('_', 1)[0], getattr(lib, name)))
-    orig_lp = _lib.lp
-
-    def lp(lib_, stem, dtype):
-        fn = orig_lp(lib_, stem, dtype)
-        assert not stem.startswith(('og_conv', 'og_stem')) or getattr(fn, 'records_conv_launch', False), stem
-        return fn
-    monkeypatch.setattr(_lib, 'lp', lp)
+    assert cx.record_launches(monkeypatch, records.add) == 2 * len(CASES)
     model = tb._bench_model(5, dev)
     eng = models.InferenceEngine(model, *shape, device=dev, dtype=torch.float16, use_graph=False)
     assert eng.strict
