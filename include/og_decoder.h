@@ -565,6 +565,60 @@ int og_draw_poses_u8(void *images, const float *poses, const int *n_persons, con
                      const unsigned char *palette, int n_colors, int N, int H, int W, int P, int K, int L,
                      float line_width, float marker_radius, float alpha, void *stream);
 
+/* ---- model-inspection views (visualization/__init__.py: draw_heatmap, draw_segments, draw_limbs, draw_offsets; evaluate.py
+ * --show-hmp-idx / --show-all-limbs / --show-limb-idx: the views of the reference's demo_batch.py:215-317) ----
+ * Rasterisers of this library's own over images uint8 RGB IN PLACE, and the two compactions that feed the segment painter.  All
+ * pointers are device pointers, no call needs a workspace, everything is ordered on `stream` and may be captured.  In all of them
+ * every operation written below is one IEEE fp32 operation, left to right as written, no contraction, divides correctly rounded.
+ *
+ * og_draw_heatmap_u8: one heat-map channel over images (N,4h,4w,3).  hm (N,C,h,w) fp32 is the stride-4 head output, lut
+ * (n_colors,3) uint8 the colour table.  For the pixel in row Y, column X of image n:
+ *   v = the element (n, channel, Y, X) og_upsample_bicubic4_f32 writes for hm (the x4 plane itself is never built);
+ *   nms == 0: u = v;  nms != 0: m = the largest of the nine v of the 3 x 3 window round (Y, X), a neighbour outside the image
+ *   counting as 0 and a NaN never as the larger one, and u = v * (m == v ? 1.f : 0.f) -- og_hmp_nms_f32's result on the x4 plane;
+ *   a NaN u leaves the pixel unwritten; otherwise t = fmin(fmax((u - vmin) / (vmax - vmin), 0), 1),
+ *   idx = (int) floorf(t * (float)(n_colors - 1) + 0.5f), and each channel c = (float) pixel; c = c + ((float) lut[idx][ch] - c) * alpha
+ *   is stored as (uint8) floorf(c + 0.5f).
+ * OG_EINVAL (nothing launched): a null pointer; a non-positive N, C, h or w, or h or w beyond INT_MAX / 4; channel outside [0, C);
+ * n_colors <= 0; vmin or vmax not finite, or vmax <= vmin; alpha outside (0, 1]; N or ceil(4h / 16) beyond 65535. */
+int og_draw_heatmap_u8(void *images, const float *hm, const unsigned char *lut, int n_colors, int N, int C, int h, int w,
+                       int channel, float vmin, float vmax, float alpha, int nms, void *stream);
+
+/* og_draw_segments_u8: line segments with end markers over images (N,H,W,3).  segs (N,S,4) fp32 rows x1, y1, x2, y2 in pixel
+ * coordinates of `images`, 16-byte aligned; n_segs int32[N], rows in use per image (clamped to [0, S]; the rows beyond are never
+ * read); line_rgb / marker_rgb: one colour each, passed by value as r | g << 8 | b << 16 (higher bits ignored).
+ * Primitives of image n, in this order: for s = 0 .. n_segs[n]-1 a capsule of radius line_width / 2 from (x1, y1) to (x2, y2) in
+ * line_rgb, then, if r_start > 0, a disc of radius r_start at (x1, y1) in marker_rgb, then, if r_end > 0, a disc of radius r_end at
+ * (x2, y2) in marker_rgb.  A segment with a non-finite coordinate is skipped whole, discs included.  Coverage, blending in
+ * primitive order, rounding and the rule that a pixel no primitive covers is never written are those of og_draw_poses_u8 above.
+ * OG_EINVAL (nothing launched): a null pointer; a non-positive N, H, W or S; alpha outside (0, 1]; a negative or non-finite
+ * line_width, r_start or r_end; segs not 16-byte aligned; 3 S beyond 2^30; N or ceil(H / 8) beyond 65535. */
+int og_draw_segments_u8(void *images, const float *segs, const int *n_segs, int N, int H, int W, int S, unsigned int line_rgb,
+                        unsigned int marker_rgb, float line_width, float r_start, float r_end, float alpha, void *stream);
+
+/* og_limbs_to_segments_f32: the candidate limbs the pairing produced as segment rows (demo_batch.py:267-276).  limbs (N,L,K,13)
+ * fp32 is the output of the og_generate_limbs_* / og_collect_limbs_* calls (columns x1, y1, v1, x2, y2, v2, ind1, ind2, len_delta,
+ * ...).  Row (l, i) of image n is kept iff (limb < 0 || l == limb) && col0 > 0 && col3 > 0 && col8 <= dist_max (a comparison with
+ * a NaN is false); a kept row gives the segment [col0, col1, col3, col4].  The kept rows of image n are written to
+ * segs (N,L*K,4) from row 0 on in ascending (l, i) order, their number to n_segs[n]; rows of segs past it are left untouched.
+ * OG_EINVAL (nothing launched): a null pointer; a non-positive N, L or K, or L * K beyond 2^28; limb >= L; segs not 16-byte aligned. */
+int og_limbs_to_segments_f32(const float *limbs, int N, int L, int K, int limb, float dist_max, float *segs, int *n_segs,
+                             void *stream);
+
+/* og_offsets_to_segments_f32: the guiding offsets of one limb type as arrows (visualization/show.py:52-64).  hm (N,C,h,w) and off
+ * (N,2L,h,w) fp32 are the stride-4 head outputs.  Grid points (Y, X), Y = 0, step, 2 step, ... < 4h and X likewise < 4w, in
+ * row-major order: S = og_offsets_segments_capacity(h, w, step) = ceil(4h / step) * ceil(4w / step) of them (0 for a non-positive
+ * argument: host arithmetic).  At a point, heat = the element og_upsample_bicubic4_f32 writes for channel joint_from of hm, U and V
+ * the elements og_upsample_bilinear4_f32 writes for channels 2 limb and 2 limb + 1 of off (bilinear: the decoder's own resampling
+ * of the offsets).  The point is kept iff heat >= thre and U and V are finite (the reference masks heat < thre and sets infinite
+ * offsets to zero: here such an arrow is dropped); a kept point gives [(float) X, (float) Y, (float) X + U, (float) Y + V].  Output
+ * as above: segs (N,S,4) in grid order from row 0 on, n_segs[n], the rest untouched.
+ * OG_EINVAL (nothing launched): a null pointer; a non-positive N, C, L, h or w, or h or w beyond 2^22; joint_from outside [0, C);
+ * limb outside [0, L); step <= 0; segs not 16-byte aligned; S beyond 2^28. */
+long og_offsets_segments_capacity(int h, int w, int step);
+int og_offsets_to_segments_f32(const float *hm, const float *off, int N, int C, int L, int h, int w, int joint_from, int limb,
+                               int step, float thre, float *segs, int *n_segs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ SIGNATURES = {
     "og_vector_l1_loss_f32": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp]),
     "og_laplace_loss_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp, _vp, _vp, _vp]),
     "og_draw_poses_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "og_draw_heatmap_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp]),
+    "og_draw_segments_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_uint, C.c_uint, _f, _f, _f, _f, _vp]),
+    "og_limbs_to_segments_f32": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "og_offsets_segments_capacity": (_l, [_i, _i, _i]),
+    "og_offsets_to_segments_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -59,7 +59,16 @@ def evaluate_cli(argv=None):
     parser.add_argument('--show-detected-poses', action='store_true', default=False,
                         help="paint every batch's poses over the network-input images on the device (visualization.draw_poses) and "
                              'write the first image of each batch to <show-dir>/<dump-name>.poses.<batch>.ppm')
-    parser.add_argument('--show-dir', default='.', type=str, help='directory of the --show-detected-poses images')
+    parser.add_argument('--show-dir', default='.', type=str, help='directory of the --show-* images')
+    parser.add_argument('--show-hmp-idx', default=None, type=int, metavar='N',
+                        help='paint heat-map channel N of the decoded maps over the first image of each batch, raw and after NMS '
+                             '(visualization.draw_heatmap): <show-dir>/<dump-name>.hmpN.<batch>.ppm and .hmpN_nms.<batch>.ppm')
+    parser.add_argument('--show-limb-idx', default=None, type=int, metavar='N',
+                        help='paint the guiding offsets of limb type N as arrows over the (whitened) first image of each batch '
+                             '(visualization.draw_offsets): <show-dir>/<dump-name>.limbN.<batch>.ppm')
+    parser.add_argument('--show-all-limbs', action='store_true', default=False,
+                        help='paint every candidate limb the pairing produced (within --dist-max) over the first image of each batch '
+                             '(visualization.draw_limbs): <show-dir>/<dump-name>.limbs.<batch>.ppm')
     g = parser.add_argument_group('apex configuration (accepted for command-line compatibility, unused)')
     g.add_argument('--local_rank', default=0, type=int)
     g.add_argument('--opt-level', type=str, default='O2')
@@ -70,6 +79,7 @@ def evaluate_cli(argv=None):
     args = parser.parse_args(argv)
     try:
         validate_test_scales(args.test_scales, args.fixed_height, args.cat_flip_offset)
+        validate_views(args)
     except ValueError as e:
         parser.error(str(e))
     args.image_dir, args.annotation_file = {
@@ -97,6 +107,35 @@ def validate_test_scales(scales, fixed_height=False, cat_flip_offset=False):
     if len(scales) > 1 and cat_flip_offset:
         raise ValueError('--test-scales with more than one scale is not implemented with --cat-flip-offset')
     return scales
+
+
+def validate_views(args):
+    """--show-hmp-idx / --show-limb-idx / --show-all-limbs: the views take 2-component offsets (no --cat-flip-offset), and an index
+    must name a heat-map channel / a limb type of the heads.  Raises ValueError.  -> whether any view is asked for."""
+    hmp_idx, limb_idx = getattr(args, 'show_hmp_idx', None), getattr(args, 'show_limb_idx', None)
+    if hmp_idx is None and limb_idx is None and not getattr(args, 'show_all_limbs', False):
+        return False
+    if getattr(args, 'cat_flip_offset', False):
+        raise ValueError('--show-hmp-idx / --show-limb-idx / --show-all-limbs are not served with --cat-flip-offset (the views take '
+                         '2-component offsets)')
+    cfg = {}
+    for name, stride in zip(args.headnets, args.strides):
+        cfg.update(decoder.factory.parse_heads(name, stride))
+    if hmp_idx is not None and not 0 <= hmp_idx < len(cfg['keypoints']):
+        raise ValueError(f"--show-hmp-idx: {hmp_idx} outside the {len(cfg['keypoints'])} heat-map channels")
+    if limb_idx is not None and not 0 <= limb_idx < len(cfg['skeleton']):
+        raise ValueError(f"--show-limb-idx: {limb_idx} outside the {len(cfg['skeleton'])} limb types")
+    return True
+
+
+def decoded_maps(proc, features, flip_test):
+    """(hm (N, C, h, w), off (N, 2L, h, w)): the stride-4 maps PostProcess.generate_limbs(features, flip_test) decodes -- the head
+    outputs of the decoded stack, with flip_test what flip_augment merges from [images | mirrored images]."""
+    hm = features[proc.hmp_index][0][proc.feat_stage]
+    off = features[proc.omp_index][0][proc.feat_stage]
+    if flip_test:
+        hm, _, off, _, _ = proc.flip_augment(hm, [], off, [], False, 2)
+    return hm, off
 
 
 def annotations_inverse(keypoints, meta):
@@ -165,7 +204,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     """The hot loop of evaluate.py:207-298.  Returns (result_keypoints, result_image_ids).
     stats: an optional dict that receives `host_enqueue_s` (per batch: host time to queue the input chain, the forward and the decoder --
     no wait in it), `engines_built`, `torch_conv_calls` (0: every engine is strict, models/engine.py), `test_scales` and
-    `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it) and, with args.show_detected_poses, `pose_images` (the files written).
+    `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it), with args.show_detected_poses `pose_images` and with
+    args.show_hmp_idx / show_limb_idx / show_all_limbs `view_images` (the files written).
     args.test_scales (--test-scales, default [1.0]): more than one scale runs the multi-scale test (enqueue_multi_scale below)."""
     if not torch.cuda.is_available():
         raise RuntimeError('run_images needs a HIP device (offsetguided_amd has no CPU path)')
@@ -195,7 +235,10 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     # once its poses are on the host they are painted over that copy on the device, in network-input coordinates (before
     # annotations_inverse), and the first image -- the reference shows batch_poses[0] -- is written as a PPM.  Off: nothing below runs
     show = bool(getattr(args, 'show_detected_poses', False))
-    if show:
+    # --show-hmp-idx / --show-all-limbs / --show-limb-idx (demo_batch.py:215-317): the handle carries paint_views' canvases
+    views = validate_views(args)
+    hmp_idx, limb_idx, all_limbs = (getattr(args, k, None) for k in ('show_hmp_idx', 'show_limb_idx', 'show_all_limbs'))
+    if show or views:
         from . import visualization
         show_dir = getattr(args, 'show_dir', '.')
         os.makedirs(show_dir, exist_ok=True)
@@ -207,10 +250,37 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
             return torch.zeros((images.shape[0],) + tuple(images.shape[2:]) + (3,), dtype=torch.uint8, device=dev)
         return visualization.denormalise_u8(images)
 
+    def paint_views(batch_idx, proc, features, flip_test, canvas):
+        """Queued on the lane's stream right after submit (the engine outputs are read before a later batch overwrites them): the
+        views of the FIRST image (canvas (1, H, W, 3) uint8) of the maps the decoder decodes -> (batch index, [(name, image)], event)."""
+        hm, off = decoded_maps(proc, features, flip_test)
+        hm, off = hm[:1], off[:1]
+        out = []
+        if hmp_idx is not None:
+            for nms in (False, True):
+                out.append((f'hmp{hmp_idx}' + ('_nms' if nms else ''), visualization.draw_heatmap(canvas.clone(), hm, hmp_idx, nms=nms)))
+        if all_limbs:
+            limbs = proc.generate_limbs(features, flip_test=flip_test, scored_off=scored_off)
+            out.append(('limbs', visualization.draw_limbs(canvas.clone(), limbs[:1], dist_max=args.dist_max)))
+        if limb_idx is not None:
+            faded = (canvas >> 1) + 128       # white blended over the image with alpha 0.5: imshow(image, alpha=0.5), show.py:61
+            out.append((f'limb{limb_idx}', visualization.draw_offsets(faded, hm, off, limb_idx, proc.skeleton)))
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return batch_idx, out, done
+
     def collect(handle):
         poses, metas = handle[:2]
         batch_poses = poses.result()
-        if len(handle) > 2:
+        if len(handle) > 3 and handle[3] is not None:
+            batch_idx, painted, done = handle[3]
+            done.synchronize()
+            for name, image in painted:
+                path = os.path.join(show_dir, f'{args.dump_name}.{name}.{batch_idx}.ppm')
+                visualization.save_ppm(path, image[0])
+                if stats is not None:
+                    stats.setdefault('view_images', []).append(path)
+        if len(handle) > 2 and handle[2] is not None:
             batch_idx, canvas = handle[2]
             visualization.draw_poses(canvas, list(batch_poses[:canvas.shape[0]]), processors[0].skeleton)
             path = os.path.join(show_dir, f'{args.dump_name}.poses.{batch_idx}.ppm')
@@ -298,7 +368,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
         cur = torch.cuda.current_stream(dev)
         inputs, tables = [], []
         base_hw = tuple(s_ // 4 for s_ in per_scale[base][0].shape[2:])
-        shown = ((batch_idx, canvas_of(per_scale[base][0], True)),) if show else ()     # the scale-1 batch is the one painted
+        shown = ((batch_idx, canvas_of(per_scale[base][0], True)) if show else None,)   # the scale-1 batch is the one painted
+        first = canvas_of(per_scale[base][0][:1], True) if views else None
         for x, metas_s in per_scale:
             aff = decoder.scale_affines(base_metas, metas_s, base_hw, tuple(s_ // 4 for s_ in x.shape[2:]))
             if n < full_batch:         # last batch of the dataset: filled up to the engine's batch, results are dropped
@@ -344,7 +415,11 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 slot[2].record(lanes[lane])
             # the accumulators are read by K1 on this lane before the lane's next batch writes them (stream order)
             feats = multiscale.merged_features(accumulators[lane], slot[0].n_stacks)
-            return (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas) + shown
+            handle = (proc.submit(feats, flip_test=False, scored_off=scored_off), base_metas) + shown
+            if views:
+                first.record_stream(lanes[lane])
+                handle += (paint_views(batch_idx, proc, feats, False, first),)
+            return handle
 
     try:
         for batch_idx, ((images, _, metas), packed) in enumerate(ahead(data_loader)):
@@ -358,7 +433,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     # ToTensor + Normalize; pinned staging packed a batch ahead, one H2D copy); metas are derived here
                     images, metas = preprocess[0](images, image_ids=[m['image_id'] for m in metas], packed=packed.result())
                 images = feeder(images)
-                shown = ((batch_idx, canvas_of(images, packed is not None)),) if show else ()
+                shown = ((batch_idx, canvas_of(images, packed is not None)) if show else None,)
+                first = canvas_of(images[:1], packed is not None) if views else None
                 full_batch = full_batch or images.shape[0]
                 if images.shape[0] < full_batch:   # last batch of the dataset: fill up to the engine's batch, results are dropped
                     images = torch.cat((images, images[-1:].expand(full_batch - images.shape[0], -1, -1, -1)))
@@ -376,6 +452,9 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     outputs = slot[0](images)
                     handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset,
                                                       scored_off=scored_off), metas) + shown
+                    if views:      # before the engine's event: the views read its outputs
+                        first.record_stream(lanes[lane])
+                        handle += (paint_views(batch_idx, processors[lane], outputs, args.flip_test, first),)
                     slot[1], slot[2] = batch_idx, torch.cuda.Event()
                     slot[2].record(lanes[lane])
             pending.append(handle)
