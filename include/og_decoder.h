@@ -619,6 +619,34 @@ long og_offsets_segments_capacity(int h, int w, int step);
 int og_offsets_to_segments_f32(const float *hm, const float *off, int N, int C, int L, int h, int w, int joint_from, int limb,
                                int step, float thre, float *segs, int *n_segs, void *stream);
 
+/* ---- training augmentation (transforms/affine.py:71-278, WarpAffineTransforms; offsetguided_amd.transforms.DeviceAugment) ----
+ * og_warp_affine_batch_u8: warp + ToTensor + Normalize of a batch in ONE launch.  `raw`, `offsets` (host long[n]) and `hw4` (host
+ * int[4 n]; entries (h, w, -, -) of image i, the last two unused here) as og_rescale_pad_normalize_batch_u8 takes them; D (host
+ * double[6 n]) = the first two rows of inv(M) of image i, row-major [a b c; d e f]: destination pixel (x, y) of the S x S square reads
+ * the source round (a x + b y + c, d x + e y + f); border3 (host, 3 bytes; the reference fills 124, 116, 104), mean3 / std3 (host, 3
+ * floats).  out fp32 (n,3,S,S) = (v / 255 - mean) / std with v the warped 8-bit value; out_u8 (device, (n,S,S,3), may be NULL)
+ * receives v itself.  The warp is this library's own integer specification -- 32 sub-pixel phases, 4-tap cubic (A = -0.75) taps
+ * scaled to 2^11 that sum to 2048, (sum + 2^21) >> 22, taps outside the image read the border colour -- written out operation by
+ * operation in csrc/augment.hip and held bit for bit to the numpy restatement tests/augment_common.py; bit parity with
+ * cv2.warpAffine(INTER_CUBIC) is NOT claimed (third-party, absent from the build).
+ * og_warp_affine_mask_u8: the same warp of single-channel planes (mask_miss, border 255 in the reference) -> out (n,S,S) uint8.
+ * OG_EINVAL (nothing launched): a null pointer; a non-positive n, S, h or w, S beyond 16384, h w beyond 2^28; a D that is not finite
+ * or with |a| S + |b| S + |c| >= 2^20 (likewise d, e, f): the kernel works in int32.
+ * og_affine_joints_f32: _affine_keypoints (:192-227) for joints (N,P,K,4) fp32 rows [x, y, v, scale] (device, 16-byte aligned),
+ * n_persons int32[N] (device; NULL: all P rows): M (host double[6 N]) the first two rows of the forward matrix, flip (host int[N]),
+ * scale (host double[N]) = sqrt(scale_x scale_y), left / right (host int[n_lr], n_lr <= 16) the mirror partners.  Per row of a
+ * person in use: x' = (m0 x + m1 y) + m2 in float64, products rounded before the sums, left to right, stored as fp32; y' with the
+ * second row; column 3 times scale in float64, rounded to fp32; with flip the rows of left[i] and right[i] change places; then
+ * v = 0 where x' <= 0 or y' <= 0 or x' > S_w or y' > S_h (on the fp32 values).  Rows beyond n_persons[n] are copied unchanged. */
+int og_warp_affine_batch_u8(const unsigned char *raw, const long *offsets, const int *hw4, int n, const double *D, int S,
+                            const unsigned char *border3, const float *mean3, const float *std3, float *out, unsigned char *out_u8,
+                            void *stream);
+int og_warp_affine_mask_u8(const unsigned char *masks, const long *offsets, const int *hw4, int n, const double *D, int S, int border,
+                           unsigned char *out, void *stream);
+int og_affine_joints_f32(const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
+                         const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr, float *out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,9 @@ SIGNATURES = {
     "og_limbs_to_segments_f32": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "og_offsets_segments_capacity": (_l, [_i, _i, _i]),
     "og_offsets_to_segments_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "og_warp_affine_batch_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_warp_affine_mask_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "og_affine_joints_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -13,6 +13,10 @@ data_std = [0.229, 0.224, 0.225]
 _SIDES = ('eye', 'ear', 'shoulder', 'elbow', 'wrist', 'hip', 'knee', 'ankle')
 COCO_KEYPOINTS = ['nose'] + [f'{lr}_{part}' for part in _SIDES for lr in ('left', 'right')]
 
+# channel indices of the left / right keypoints, partner by partner (config/coco_data.py:76-77)
+LEFT_INDEX = [i for i, name in enumerate(COCO_KEYPOINTS) if name.startswith('left_')]
+RIGHT_INDEX = [i for i, name in enumerate(COCO_KEYPOINTS) if name.startswith('right_')]
+
 # mirror-image partner of every sided keypoint
 HFLIP = {f'{a}_{p}': f'{b}_{p}' for p in _SIDES for a, b in (('left', 'right'), ('right', 'left'))}
 

@@ -10,16 +10,18 @@
 
 One process per GPU (`python -m torch.distributed.run --nproc-per-node N -m offsetguided_amd.train_dist`);
 without COCO on disk the loop runs on synthetic encoder-style targets (GT heatmaps, patch offsets with
-inf outside the patches, instance scales, mask_miss).
+inf outside the patches, instance scales, mask_miss).  --augment: the pool holds raw uint8 images and un-augmented annotations,
+and every step warps a new random crop on the device (transforms.DeviceAugment = the reference's WarpAffineTransforms).
 """
 import argparse
 import os
+import random
 import time
 
 import numpy as np
 import torch
 
-from . import encoder, models, sharding, synth
+from . import _lib, encoder, models, sharding, synth, transforms
 from .config import coco_data as cd
 from .utils import AverageMeter, adjust_learning_rate
 
@@ -44,6 +46,17 @@ def train_cli(argv=None):
     p.add_argument('--bench-warmup', default=5, type=int)
     p.add_argument('--grad-compress', default='bf16', choices=['none', 'bf16'],
                    help='DDP gradient all-reduce payload: fp32 (750.9 MB) or bf16-compressed (375.5 MB)')
+    g = p.add_argument_group('training parameters for warp affine (data/factory.py:84-104)')
+    g.add_argument('--augment', action='store_true', default=False,
+                   help='augment on the device: raw uint8 images + annotations in the pool, a new random WarpAffineTransforms crop '
+                        '(flip, rotate, scale, stretch, translate) of every batch in every step')
+    g.add_argument('--flip-prob', default=0.5, type=float, help='the probability to flip the input image')
+    g.add_argument('--max-rotate', default=45, type=float, help='upper bound of the image rotation during augmentation')
+    g.add_argument('--min-scale', default=0.5, type=float, help='lower bound of the relative image scale during augmentation')
+    g.add_argument('--max-scale', default=2.0, type=float, help='upper bound of the relative image scale during augmentation')
+    g.add_argument('--min-stretch', default=0.95, type=float, help='lower bound of the relative image length stretch')
+    g.add_argument('--max-stretch', default=1.05, type=float, help='upper bound of the relative image length stretch')
+    g.add_argument('--max-translate', default=150, type=int, help='upper bound of shifting the image during augmentation')
     g = p.add_argument_group('optimizer configuration')
     g.add_argument('--optimizer', type=str, default='adam', choices=['sgd', 'adam'])
     g.add_argument('--learning-rate', type=float, default=2.5e-4, help='learning rate for world size 1')
@@ -77,10 +90,11 @@ def synthetic_targets(seed, batch, size, device, *, background=False, jitter=Fal
     return [(t(hm), bg, jit, mask), (t(off), sc, t(ps), mask)]
 
 
-def synthetic_annotations(seed, batch, size):
+def synthetic_annotations(seed, batch, size, width=None):
     """Annotation-style input of the encoders: joints (N,P,17,4) fp32 [x, y, v, scale] padded to P persons, and the
-    person count per image (transforms/annotations.py:46-50 layout; the scale column plays the keypoint scale)."""
-    scenes = [synth.make_scene(synth.HashRng(seed * 1000003 + i), size, size) for i in range(batch)]
+    person count per image (transforms/annotations.py:46-50 layout; the scale column plays the keypoint scale).  Scenes are
+    size x size, or size rows x width columns."""
+    scenes = [synth.make_scene(synth.HashRng(seed * 1000003 + i), size, width or size) for i in range(batch)]
     p_max = max(xy.shape[0] for xy, _, _ in scenes)
     joints = np.zeros((batch, p_max, 17, 4), np.float32)
     for i, (xy, vis, _) in enumerate(scenes):
@@ -90,6 +104,41 @@ def synthetic_annotations(seed, batch, size):
         extent = (xy[..., 1].max(1) - xy[..., 1].min(1)).astype(np.float32)            # person height in pixels
         joints[i, :p, :, 3] = (extent[:, None] * np.asarray(cd.COCO_PERSON_SIGMAS, np.float32)[None]).astype(np.float32)
     return joints, np.array([xy.shape[0] for xy, _, _ in scenes], np.int32)
+
+
+def synthetic_raw_images(seed, joints, n_persons, height, width):
+    """Raw uint8 (height, width, 3) images for synthetic annotations: flat limbs of the annotated skeletons on noise."""
+    images = []
+    for i in range(joints.shape[0]):
+        rs = np.random.RandomState(seed * 1009 + i)
+        im = rs.randint(64, 192, (height, width, 3)).astype(np.uint8)
+        for p in range(int(n_persons[i])):
+            colour = rs.randint(0, 256, 3).astype(np.uint8)
+            for a, b in cd.COCO_PERSON_SKELETON:
+                ja, jb = joints[i, p, a], joints[i, p, b]
+                if ja[2] > 0 and jb[2] > 0:
+                    t = np.linspace(0.0, 1.0, int(max(abs(jb[0] - ja[0]), abs(jb[1] - ja[1]))) + 2)[:, None]
+                    xy = np.rint(ja[None, :2] * (1 - t) + jb[None, :2] * t).astype(np.int64)
+                    for dy in (-1, 0, 1):
+                        for dx in (-1, 0, 1):
+                            im[np.clip(xy[:, 1] + dy, 0, height - 1), np.clip(xy[:, 0] + dx, 0, width - 1)] = colour
+        images.append(im)
+    return images
+
+
+def augmented_batch(augment, entry, rng, events=None):
+    """One training batch from a pool entry of raw images + annotations: a new random crop (transforms.DeviceAugment) -> (images,
+    (joints, n_persons)) on the device.  events: a list that receives a (start, end) pair of HIP timing events round the augment calls."""
+    raws, joints, n_persons, n_persons_dev = entry
+    stream = torch.cuda.current_stream(augment.device)
+    if events is not None:
+        start, end = _lib.TimingEvent(), _lib.TimingEvent()
+        start.record(stream)
+    images, joints_dev, _, _ = augment(raws, joints, n_persons, rng=rng)
+    if events is not None:
+        end.record(stream)
+        events.append((start, end))
+    return images.contiguous(memory_format=torch.channels_last), (joints_dev, n_persons_dev)
 
 
 def encode_targets(encoders, joints, n_persons):
@@ -134,7 +183,7 @@ def describe_losses(args):
     return ' + '.join(parts) + ' losses' + (', sqrt' if args.sqrt_re else '') + ('' if args.fused_losses else ', torch-formulated')
 
 
-def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world):
+def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment=None, rng=None):
     """BASELINE configs[4]: step time of the DDP training step (fused HIP losses, device-side GT encoding, bf16 autocast)
     and the gradient all-reduce's bus bandwidth.  The all-reduce overlaps backward inside the step, so its bandwidth is
     measured on its own: the same payload (one flat buffer of the gradients' size, the bucketed hook's dtype) reduced
@@ -145,11 +194,16 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
     use_cuda = dev.type == 'cuda'
     dist = torch.distributed
 
+    augment_events = []
+
     def run(n, first, sync_grads=True):
         ctx = contextlib.nullcontext() if (sync_grads or world == 1) else model.no_sync()
         with ctx:
             for step in range(first, first + n):
-                images, annos = pool[step % len(pool)]
+                if augment is not None:
+                    images, annos = augmented_batch(augment, pool[step % len(pool)], rng, augment_events)
+                else:
+                    images, annos = pool[step % len(pool)]
                 if encoders is not None:
                     annos = encode_targets(encoders, *annos)
                 train_step(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None)
@@ -163,7 +217,13 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
 
     model.train()
     run(max(args.bench_warmup, 1), 0)
+    del augment_events[:]
     step_s = timed(args.bench_steps, args.bench_warmup)
+    extra = {}
+    if augment is not None:
+        torch.cuda.synchronize(dev)               # the events are complete before they are read
+        us =[a.elapsed_time(b) * 1e3 for a, b in augment_events]
+        extra['augment_us'] = round(sum(us) / len(us), 1)
     nosync_s = timed(max(args.bench_steps // 2, 1), 0, sync_grads=False) if world > 1 else step_s
     n_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
     payload_dtype = torch.bfloat16 if (args.grad_compress == 'bf16' and use_cuda) else torch.float32
@@ -193,7 +253,8 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
                        'sync_bn': bool(args.sync_bn and world > 1), 'grad_payload': str(payload_dtype).replace('torch.', '')},
             'grad_allreduce': {'bytes': nbytes, 'ms': comm_ms, 'bus_GBps': bus,
                                'exposed_comm_ms': round(max(step_s - nosync_s, 0.0) * 1e3, 2) if world > 1 else 0.0},
-            'data': 'synthetic annotations, GT encoded on the device'}))
+            'data': 'synthetic raw images, augmented and encoded on the device' if augment is not None
+                    else 'synthetic annotations, GT encoded on the device', **extra}))
     if dist.is_initialized():
         dist.destroy_process_group()
 
@@ -244,13 +305,22 @@ def main(argv=None):
     # would measure numpy, not the training step)
     # On the GPU the pool holds ANNOTATIONS and the targets are encoded on the device inside every step
     # (the reference's numpy encoder manages 17 samples/s per dataloader worker, data/factory.py:284).
-    pool, encoders = [], None
+    pool, encoders, augment, aug_rng = [], None, None, random.Random(1000 * rank + 7)
+    if args.augment and not use_cuda:
+        raise _lib.OgError('--augment warps on the device: it needs a GPU (offsetguided_amd has no CPU path)')
     if use_cuda:
         encoder.HeatMaps.include_jitter_offset = args.include_jitter_offset
         encoder.HeatMaps.include_background = args.include_background
         encoder.OffsetMaps.include_scale = args.include_scale
         encoders = encoder.factory_heads(['hmp', 'omp'], args.square_length, [4, 4], dev)
-    for i in range(4):
+    if args.augment:
+        # raw uint8 images on 640 x 480 canvases and their un-augmented annotations; every step draws a new crop of its entry
+        augment = transforms.DeviceAugment(args.square_length, args, device=dev)
+        for i in range(4):
+            joints, n_persons = synthetic_annotations(1000 * rank + i, args.batch_size, 480, 640)
+            pool.append((synthetic_raw_images(1000 * rank + i, joints, n_persons, 480, 640), joints, n_persons,
+                         torch.from_numpy(n_persons).to(dev)))
+    for i in range(0 if args.augment else 4):
         imgs = torch.randn(args.batch_size, 3, args.square_length, args.square_length, device=dev)
         if use_cuda:
             imgs = imgs.contiguous(memory_format=torch.channels_last)
@@ -261,7 +331,7 @@ def main(argv=None):
                                                  background=args.include_background, jitter=args.include_jitter_offset,
                                                  scale=args.include_scale)))
     if args.bench:
-        return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world)
+        return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment, aug_rng)
     batch_time = AverageMeter()   # over the whole run: the first steps (MIOpen find, allocator warm-up) do not bias an epoch
     # --epochs MORE epochs after a resume, as the reference counts them (train_dist.py:269)
     for epoch in range(start_epoch, start_epoch + args.epochs):
@@ -269,7 +339,10 @@ def main(argv=None):
         losses, end, last_print = AverageMeter(), time.time(), -1
         for step in range(args.steps_per_epoch):
             adjust_learning_rate(args.learning_rate, world, optimizer, epoch, step, args.steps_per_epoch, args.warmup)
-            images, annos = pool[step % len(pool)]
+            if augment is not None:
+                images, annos = augmented_batch(augment, pool[step % len(pool)], aug_rng)
+            else:
+                images, annos = pool[step % len(pool)]
             if encoders is not None:
                 annos = encode_targets(encoders, *annos)
             loss, _ = train_step(model, criterion, optimizer, images, annos, args.lambdas,
