@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define OG_ABI_VERSION 3
+#define OG_ABI_VERSION 4
 
 #define OG_OK 0
 #define OG_EINVAL (-1)    /* bad argument (shape, k, alignment, null pointer)        */
@@ -91,98 +91,85 @@ int og_upsample_nms_topk_f32(const float *hmps_lr, long planes, int h, int w, in
 
 size_t og_topk_workspace_bytes(long planes, int H, int W, int k);
 
-/* ---- a9+a10: LimbsCollect.generate_limbs  decoder/collect.py:62-236 (+ _channel_dets :246-254) ----
- * scores/inds : (N,C,k) from og_nms_topk_f32 on (N,C,H,W) hi-res heatmaps
- * offs        : off_is_lowres ? (N,2L,H/4,W/4) stride-4 head output, bilinearly sampled at the
- *               from-peaks exactly as factory.py:77-78 + collect.py:143-147 would
- *             : (N,2L,H,W) hi-res offsets, gathered
- * jf/jt       : device int32[L] from/to joint channel per limb (LimbsCollect.pack_jtypes)
- * limbs       : (N,L,k,13) [x1,y1,v1,x2,y2,v2,ind1,ind2,min_dist,len,score,scale1,scale2]
- * No scale / jitter heads (scales are the constant 4, collect.py:117-122). */
-int og_collect_limbs_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                         int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                         float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream);
+/* ---- a8+a9+a10: LimbsCollect.generate_limbs  decoder/collect.py:62-236 (+ _channel_dets :246-254) behind ONE descriptor ----
+ * limbs (N,L,k,13) [x1,y1,v1,x2,y2,v2,ind1,ind2,min_dist,len,score,scale1,scale2].  Every form of the call is a setting of
+ * OgLimbsDesc; which settings go together is checked in one place (validate_limbs_desc, csrc/nms_topk.hip).  The entry points of
+ * ABI 3 (bench.py and the committed profiles still print their names) are these settings:
+ *   og_generate_limbs_f32 (ABI 3)             hm_lowres 0, no perm; the reserved `flags` is gone
+ *   og_generate_limbs_flip_f32                hm_lowres 0, off_lowres 1, vector_nd 2, limb_perm + reserve_mask
+ *   og_generate_limbs_fused_f32               hm_lowres 1, off_lowres 1 (H, W = 4h, 4w)
+ *   og_generate_limbs_fused_flip_f32          ... + kp_perm, limb_perm + reserve_mask, vector_nd 2
+ *   og_generate_limbs_fused_scored_f32        og_generate_limbs_fused_f32 + score_ksize, vector_nd 2
+ *   og_generate_limbs_fused_flip_scored_f32   og_generate_limbs_fused_flip_f32 + score_ksize
+ *   og_generate_limbs_fused_flip_heads_f32    og_generate_limbs_fused_flip[_scored]_f32 + scales (mode 2 / 3) and / or jitter (mode 3)
+ *   og_collect_limbs{,_nd,_ex,_full}_f32      og_collect_limbs_f32 with the same descriptor (hmps unused unless score_ksize) */
+typedef struct OgLimbsDesc {
+    uint32_t size;             /* sizeof(OgLimbsDesc): anything else is refused (OG_EINVAL, "descriptor size") */
+    /* heat maps: hm_lowres 0 = (N,C,H,W) at input resolution; 1 = the stride-4 head output (N,C,H/4,W/4), the x4 bicubic of
+     * decoder/factory.py:74-75 runs inside the band kernel (bit-identical to og_upsample_bicubic4_f32; K1-fused, the production path) */
+    const float *hmps;
+    int hm_lowres;
+    /* flip-test fold of the heat maps (hm_lowres only): hmps (2N,C,H/4,W/4) = [images | mirrored images], every source value
+     * (a + flipW(b)[kp_perm]) / 2 as og_flip_merge_f32 would have written it; int32[C] device array (config.heatmap_hflip) or NULL */
+    const int32_t *kp_perm;
+    /* guiding offsets: off_lowres 1 = (N,vector_nd*L,H/4,W/4) stride-4 head output, bilinearly sampled at the from-peaks exactly as
+     * factory.py:77-78 + collect.py:143-147 would; 0 = (N,vector_nd*L,H,W), gathered.  vector_nd 2, or 4 = the `cat_flip_offs` form
+     * (factory.py:115-127: offs from og_flip_cat_f32, match distance = the 4-D norm of (guide - to, guide' - to)) */
+    const float *offs;
+    int off_lowres;
+    int vector_nd;
+    /* flip-test fold of the offsets (both or neither; off_lowres, 2 components): offs (2N,2L,H/4,W/4) of [images | mirrored images],
+     * every tap (a + flipW(b)[limb_perm]) / 2, x negated, the limbs of reserve_mask un-averaged; int32[L] device arrays
+     * (config.offset_hflip).  og_generate_limbs_f32 only.  With hm_lowres the heat maps are folded as well (kp_perm) */
+    const int32_t *limb_perm;
+    const int32_t *reserve_mask;
+    /* 0, or odd 1..7: scored_off (decoder/offset.py:8-43) inside the pairing -- every bilinear tap of the offset sampling is the refined
+     * value of its stride-4 cell, computed on the spot from the (flip-merged-on-load) window of hmps, so the refined tensor is never
+     * built; needs hm_lowres, off_lowres, 2 components.  Bit-identical to (og_flip_merge_f32 +) og_scored_offset_f32 in front */
+    int score_ksize;
+    /* keypoint-scale head (collect.py:111-122, :257-262): limbs columns 11 / 12 = the scale map of the from / to joint channel at the
+     * from-peak / the matched to-peak instead of the constant 4.  scales_mode 0: no head (scales NULL); 1: (N,C,H,W), gathered; 2 / 3:
+     * (N,C,H/4,W/4) = the head output, sampled as F.interpolate(x4, 'bicubic' / 'bilinear') would (factory.py:80-82) */
+    const float *scales;
+    int scales_mode;
+    /* jitter-offset head (collect.py:127-138, :154-165, :210-214): (N,2,..) = the two shared refinement channels; jitter_mode 0: none;
+     * 1: maps at input resolution; 3: stride-4 head output, sampled as F.interpolate(x4, 'bilinear') would (factory.py:84-88).  The guide
+     * point is refined by the vector read at its truncated coordinates ([x][y] indexing of the reference: square inputs only) and the
+     * limb's end points move by the vectors at their own peaks.  With hm_lowres only the stride-4 modes (scales 2 / 3, jitter 3); with the
+     * flip fold (hm_lowres only) both maps are the (2N,..) pairs, every tap the value og_flip_merge_heads_f32 would have written -- a
+     * kernel instantiation of its own, the other forms keep their registers and LDS */
+    const float *jitter;
+    int jitter_mode;
+    int N, C, H, W;            /* images, joint channels, INPUT-resolution size (also with hm_lowres: the head output is H/4 x W/4) */
+    const int32_t *jf;         /* device int32[L] from / to joint channel per limb (LimbsCollect.pack_jtypes) */
+    const int32_t *jt;
+    int L, k;
+    float thre_hmp, min_len, resize_factor;
+    /* outputs: the optional (N,C,k) lists of the joint_dets stage (both or neither; og_generate_limbs_f32 only) and the limbs */
+    float *topk_scores;
+    int64_t *topk_inds;
+    float *limbs;
+} OgLimbsDesc;
 
-/* Same with `vector_nd` offset components per limb: 2 = og_collect_limbs_f32; 4 = the `cat_flip_offs` form
- * (decoder/factory.py:115-127 -> collect.py:62 vector_nd=4): offs (N,4L,..) from og_flip_cat_f32, match distance =
- * the 4-D norm of (guide - to, guide' - to). */
-int og_collect_limbs_nd_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                            int vector_nd, int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L,
-                            int k, float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream);
+/* = og_nms_topk_f32 / og_upsample_nms_topk_f32 (joint_dets, decoder/heatmap.py:52-59) followed by og_collect_limbs_f32 on the same
+ * descriptor, bit-identical limbs.  Two launches queued back to back -- band top-k, then ONE kernel that merges the band lists and
+ * pairs the limbs.  Shapes whose merge-and-pair stage does not fit the LDS (large k) finish with og_collect_limbs_f32's kernel; with
+ * the flip fold they are refused with OG_EUNSUPPORTED: take the unfolded route (og_flip_merge_f32 in front).
+ * workspace: og_generate_limbs_workspace_bytes(N, C, H, W, k) bytes, 16-byte aligned, ZERO-FILLED by the caller (hipMemset) before its
+ * first use; every call leaves it ready for the next one (any shape).  Its first 64 KiB are reserved and stay zero. */
+int og_generate_limbs_f32(const OgLimbsDesc *d, void *workspace, size_t workspace_bytes, void *stream);
 
-/* Same with the keypoint-scale head (decoder/collect.py:111-122, :257-262): limbs columns 11 / 12 = the scale map of
- * the from / to joint channel at the from-peak / the matched to-peak instead of the constant 4.
- * scales_mode 0: no head (scales NULL); 1: scales (N,C,H,W) at input resolution, gathered; 2 / 3: scales (N,C,H/4,W/4)
- * = the head output, sampled as F.interpolate(x4, 'bicubic' / 'bilinear') would (decoder/factory.py:80-82). */
-int og_collect_limbs_ex_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                            int vector_nd, const float *scales, int scales_mode, int N, int C, int H, int W,
-                            const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                            float resize_factor, float *limbs, void *stream);
-
-/* ... and with the jitter-offset head (decoder/collect.py:127-138, :154-165, :210-214; include_jitter_offset with
- * use_jitter_offset): jitter (N,2,..) = the two shared refinement channels; jitter_mode 0: none; 1: maps at input
- * resolution; 3: stride-4 head output, sampled as F.interpolate(x4, 'bilinear') would (decoder/factory.py:84-88).
- * The guide point is refined by the vector read at its truncated coordinates ([x][y] indexing of the reference:
- * square inputs only) and the limb's end points move by the vectors at their own peaks. */
-int og_collect_limbs_full_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                              int vector_nd, const float *scales, int scales_mode, const float *jitter, int jitter_mode,
-                              int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                              float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream);
-
-/* ---- a8+a9+a10 in ONE call: LimbsCollect.generate_limbs  decoder/collect.py:62-236 on (N,C,H,W) hi-res heatmaps ----
- * = og_nms_topk_f32 (joint_dets, decoder/heatmap.py:52-59) followed by og_collect_limbs_full_f32, same arguments and
- * bit-identical limbs.  topk_scores / topk_inds: optional (N,C,k) outputs of the joint_dets stage (both or neither).
- * Two launches queued back to back -- band top-k, then ONE kernel that merges the band lists and pairs the limbs (shapes
- * whose merge stage does not fit the LDS finish with og_collect_limbs_full_f32's kernel).  `flags` is reserved: pass 0 (rounds 2
- * and 3 selected two one-launch forms there -- a persistent kernel and the merge + pairing by last arrivers of the band launch --
- * both bit-identical and slower; they live on as tools/experiments/k1_single.inc / EXPERIMENTS.md).
- * workspace: og_generate_limbs_workspace_bytes(N, C, H, W, k) bytes, 16-byte aligned, ZERO-FILLED by the caller
- * (hipMemset) before its first use; every call leaves it ready for the next one (any shape).
- */
-int og_generate_limbs_f32(const float *hmps_hr, const float *offs, int off_is_lowres, int vector_nd,
-                          const float *scales, int scales_mode, const float *jitter, int jitter_mode,
-                          int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                          float thre_hmp, float min_len, float resize_factor, float *topk_scores,
-                          int64_t *topk_inds, float *limbs, int flags, void *workspace, size_t workspace_bytes,
-                          void *stream);
+/* The pairing alone: scores / inds (N,C,k) from og_nms_topk_f32 on the (N,C,H,W) heat maps.  Reads d->hmps only with score_ksize (the
+ * stride-4 heat maps the refinement weighs with); limb_perm is refused (OG_EUNSUPPORTED); topk_scores / topk_inds are ignored. */
+int og_collect_limbs_f32(const float *scores, const int64_t *inds, const OgLimbsDesc *d, void *stream);
 
 size_t og_generate_limbs_workspace_bytes(int N, int C, int H, int W, int k);
 
 /* ---- flip-test without a merge pass: PostProcess.flip_augment (decoder/factory.py:98-146, the averaged form) folded into the
- * loads of its two consumers.  Both take the head outputs of [images | mirrored images] (2N leading) and compute every value
- * they read exactly as og_flip_merge_f32 would have written it -- (a + flipW(b)[perm]) / 2, x offsets negated, the limbs of
- * `reserve_mask` un-averaged -- so the results are bit-identical to og_flip_merge_f32 followed by og_upsample_bicubic4_f32 /
- * og_generate_limbs_f32 (2-component offsets sampled from the stride-4 map, no scale / jitter head), one pass over the
- * 3 x 5.6 MB/img stride-4 maps and one launch fewer.
- *   og_upsample_bicubic4_flip_f32: hm_pair (2N,C,h,w) -> dst (N,C,4h,4w); kp_perm int32[C] (config.heatmap_hflip).
- *   og_generate_limbs_flip_f32: offs_pair (2N,2L,H/4,W/4); limb_perm / reserve_mask int32[L] (config.offset_hflip); the other
- *     arguments, the workspace and the outputs as og_generate_limbs_f32. */
+ * loads of its consumers (OgLimbsDesc.kp_perm / limb_perm above, and this one for the unfused route): hm_pair (2N,C,h,w) of
+ * [images | mirrored images] -> dst (N,C,4h,4w), every value (a + flipW(b)[kp_perm]) / 2 exactly as og_flip_merge_f32 would have
+ * written it; kp_perm int32[C] (config.heatmap_hflip).  Bit-identical to og_flip_merge_f32 + og_upsample_bicubic4_f32. */
 int og_upsample_bicubic4_flip_f32(const float *hm_pair, const int32_t *kp_perm, int N, int C, int h, int w, float *dst, void *stream);
-int og_generate_limbs_flip_f32(const float *hmps_hr, const float *offs_pair, const int32_t *limb_perm, const int32_t *reserve_mask,
-                               int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp,
-                               float min_len, float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
-                               void *workspace, size_t workspace_bytes, void *stream);
-
-/* ---- K1-fused (the production path): generate_limbs straight from the STRIDE-4 head outputs.  The x4 bicubic of
- * decoder/factory.py:74-75 runs inside the NMS kernel (bit-identical to og_upsample_bicubic4_f32), offsets / scale / jitter maps are
- * sampled at the peaks: neither hi-res tensor of factory.py:74-88 is built.  Same limbs, same optional (N,C,k) lists, same two
- * launches and the same workspace as og_generate_limbs_f32 on (N,C,4h,4w): og_generate_limbs_workspace_bytes(N, C, 4h, 4w, k).
- *   hmps_lr (N,C,h,w), offs_lr (N,vector_nd*L,h,w); scales_lr (N,C,h,w) with scales_mode 2 / 3 (bicubic / bilinear) or NULL / 0;
- *   jitter_lr (N,2,h,w) with jitter_mode 3 or NULL / 0.
- * og_generate_limbs_fused_flip_f32: flip-test (decoder/factory.py:98-146, averaged form, 2-component offsets, no scale / jitter
- *   head) folded into both consumers: hm_pair_lr (2N,C,h,w), offs_pair_lr (2N,2L,h,w) = head outputs of [images | mirrored images];
- *   kp_perm int32[C], limb_perm / reserve_mask int32[L] device arrays (config.heatmap_hflip / offset_hflip).  Bit-identical to
- *   og_flip_merge_f32 + og_generate_limbs_fused_f32. */
-int og_generate_limbs_fused_f32(const float *hmps_lr, const float *offs_lr, int vector_nd, const float *scales_lr, int scales_mode,
-                                const float *jitter_lr, int jitter_mode, int N, int C, int h, int w, const int32_t *jf,
-                                const int32_t *jt, int L, int k, float thre_hmp, float min_len, float resize_factor,
-                                float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace, size_t workspace_bytes,
-                                void *stream);
-int og_generate_limbs_fused_flip_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                     const int32_t *limb_perm, const int32_t *reserve_mask, int N, int C, int h, int w,
-                                     const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                     float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace,
-                                     size_t workspace_bytes, void *stream);
 
 /* ---- a13: scored_offset  decoder/offset.py:8-43 (PostProcess: kernel_size 3, decoder/factory.py:70-72) ----
  * Heatmap-weighted offset refinement on the stride-4 maps: hm (N,C,h,w), off / out (N,2L,h,w) contiguous fp32, out must not alias off;
@@ -194,35 +181,9 @@ int og_generate_limbs_fused_flip_f32(const float *hm_pair_lr, const int32_t *kp_
  * (LDS-tiled row bands, 16-byte accesses when w % 4 == 0 and the pointers are 16-byte aligned, a scalar path otherwise); no
  * allocation, no synchronisation, graph-capturable.  jf[l] in [0, C) is checked here when the table is host-visible (pinned) and is
  * the caller's duty otherwise, as for the other joint tables (a workgroup whose entry is out of range writes nothing).
- * og_generate_limbs_fused_scored_f32 / og_generate_limbs_fused_flip_scored_f32: the K1-fused forms with that refinement INSIDE the
- *   pairing -- every bilinear tap of the offset sampling is the refined value of its stride-4 cell, computed on the spot from the
- *   (flip-merged-on-load) window, so the refined tensor is never built; 2-component offsets; the other arguments as the unrefined
- *   forms.  Bit-identical to (og_flip_merge_f32 +) og_scored_offset_f32 + og_generate_limbs_fused_f32. */
+ * OgLimbsDesc.score_ksize runs the same refinement inside the limb pairing. */
 int og_scored_offset_f32(const float *hm, const float *off, int N, int C, int L, int h, int w, const int32_t *jf, int ksize,
                          float *out, void *stream);
-int og_generate_limbs_fused_scored_f32(const float *hmps_lr, const float *offs_lr, int ksize, const float *scales_lr, int scales_mode,
-                                       const float *jitter_lr, int jitter_mode, int N, int C, int h, int w, const int32_t *jf,
-                                       const int32_t *jt, int L, int k, float thre_hmp, float min_len, float resize_factor,
-                                       float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace, size_t workspace_bytes,
-                                       void *stream);
-int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                            const int32_t *limb_perm, const int32_t *reserve_mask, int ksize, int N, int C, int h,
-                                            int w, const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                            float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
-                                            void *workspace, size_t workspace_bytes, void *stream);
-
-/* The flip form with the optional heads folded in as well: scales_pair_lr (2N,C,h,w) with scales_mode 2 / 3 and / or jitter_pair_lr
- * (2N,2,h,w) with jitter_mode 3 (square inputs, as og_generate_limbs_fused_f32), the head outputs of [images | mirrored images]; at
- * least one of them.  Every scale / jitter tap is the value og_flip_merge_heads_f32 would have written.  ksize 0: unrefined offsets;
- * odd 1..7: scored_off as og_generate_limbs_fused_flip_scored_f32.  Bit-identical to og_flip_merge_f32 + og_flip_merge_heads_f32 +
- * og_generate_limbs_fused_f32 / _scored_f32; a kernel instantiation of its own (the forms above keep their registers and LDS).
- * OG_EUNSUPPORTED when the merge-and-pair stage does not fit the LDS (large k), as the other flip forms: take the unfolded route. */
-int og_generate_limbs_fused_flip_heads_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                           const int32_t *limb_perm, const int32_t *reserve_mask, int ksize,
-                                           const float *scales_pair_lr, int scales_mode, const float *jitter_pair_lr, int jitter_mode,
-                                           int N, int C, int h, int w, const int32_t *jf, const int32_t *jt, int L, int k,
-                                           float thre_hmp, float min_len, float resize_factor, float *topk_scores, int64_t *topk_inds,
-                                           float *limbs, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- a12: GreedyGroup.group_skeletons  decoder/group.py:39-185 (+ :187-240) ----
  * One workgroup per image, device resident (replaces .cpu().numpy() + Pool.starmap,

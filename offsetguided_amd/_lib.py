@@ -15,9 +15,21 @@ if os.environ.get("OG_DECODER_LIB"):  # alternative build of the same ABI (kerne
     LIB_PATH = os.environ["OG_DECODER_LIB"]
 
 OG_OK, OG_EINVAL, OG_ENOSPC, OG_EHIP, OG_EUNSUPPORTED = 0, -1, -2, -3, -4
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
+
+
+class LimbsDesc(C.Structure):
+    """OgLimbsDesc (include/og_decoder.h), field for field.  LimbsDesc(name=value, ...) sets `size`; a tensor stands for its device pointer."""
+    _fields_ = [("size", C.c_uint32), ("hmps", _vp), ("hm_lowres", _i), ("kp_perm", _vp), ("offs", _vp), ("off_lowres", _i), ("vector_nd", _i),
+                ("limb_perm", _vp), ("reserve_mask", _vp), ("score_ksize", _i), ("scales", _vp), ("scales_mode", _i), ("jitter", _vp),
+                ("jitter_mode", _i), ("N", _i), ("C", _i), ("H", _i), ("W", _i), ("jf", _vp), ("jt", _vp), ("L", _i), ("k", _i),
+                ("thre_hmp", _f), ("min_len", _f), ("resize_factor", _f), ("topk_scores", _vp), ("topk_inds", _vp), ("limbs", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(size=C.sizeof(LimbsDesc), **{k: v.data_ptr() if isinstance(v, torch.Tensor) else v for k, v in fields.items()})
+
 
 # name -> (restype, argtypes); mirrors include/og_decoder.h one to one
 SIGNATURES = {
@@ -27,26 +39,15 @@ SIGNATURES = {
     "og_upsample_bicubic4_f32": (_i, [_vp, _l, _i, _i, _vp, _vp]),
     "og_upsample_bilinear4_f32": (_i, [_vp, _l, _i, _i, _vp, _vp]),
     "og_upsample_bicubic4_flip_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "og_generate_limbs_flip_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_hmp_nms_f32": (_i, [_vp, _l, _i, _i, _vp, _vp]),
     "og_hmp_nms_k_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp]),
     "og_topk_channel_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "og_nms_topk_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "og_generate_limbs_fused_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "og_generate_limbs_fused_flip_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_scored_offset_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "og_generate_limbs_fused_scored_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "og_generate_limbs_fused_flip_scored_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "og_generate_limbs_fused_flip_heads_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f,
-                                                    _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_upsample_nms_topk_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "og_topk_workspace_bytes": (_sz, [_l, _i, _i, _i]),
-    "og_collect_limbs_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
-    "og_collect_limbs_nd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
-    "og_collect_limbs_ex_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
-    "og_collect_limbs_full_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
-    "og_generate_limbs_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                                   _i, _vp, _sz, _vp]),
+    "og_collect_limbs_f32": (_i, [_vp, _vp, C.POINTER(LimbsDesc), _vp]),
+    "og_generate_limbs_f32": (_i, [C.POINTER(LimbsDesc), _vp, _sz, _vp]),
     "og_generate_limbs_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "og_greedy_group_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _d, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -116,12 +117,11 @@ _lib = None
 
 def lp(lib, stem, dtype):
     """Entry point of the 16-bit-type specific family for a torch dtype: lp(lib, 'og_conv2d', torch.float16) -> og_conv2d_f16."""
-    import torch as _t
-    return getattr(lib, stem + ('_f16' if dtype == _t.float16 else '_bf16'))
+    return getattr(lib, stem + ('_f16' if dtype == torch.float16 else '_bf16'))
 
 
 class OgError(RuntimeError):
-    pass
+    code = None     # the OG_E* value of a refused call (check)
 
 
 def load():
@@ -151,8 +151,9 @@ def load():
 
 def check(rc, lib=None):
     if rc != OG_OK:
-        msg = (lib or load()).og_last_error().decode(errors="replace")
-        raise OgError(f"libog_decoder: {msg} (code {rc})")
+        err = OgError(f"libog_decoder: {(lib or load()).og_last_error().decode(errors='replace')} (code {rc})")
+        err.code = rc
+        raise err
 
 
 def require_device(t, name, dtype=torch.float32):
@@ -251,11 +252,9 @@ _const_cache = {}
 def int_table(values, device):
     """Small int32 device table (skeleton / permutation), cached per device."""
     key = (tuple(int(v) for v in values), device.index)
-    t = _const_cache.get(key)
-    if t is None:
-        t = torch.tensor(key[0], dtype=torch.int32, device=device)
-        _const_cache[key] = t
-    return t
+    if key not in _const_cache:
+        _const_cache[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
+    return _const_cache[key]
 
 
 # ---- optional per-stage device timing (bench.py) -------------------------------------------

@@ -31,68 +31,22 @@ collect_limbs_scored_kernel(const float *__restrict__ scores, const int64_t *__r
 
 }  // namespace
 
-int og_collect_limbs_scored_impl(const char *name, const float *scores, const int64_t *inds, int N, const og_collect::ScoredArgs &a,
-                                 void *stream)
+// The launch alone, for the two entry points (csrc/nms_topk.hip), which have validated their descriptor: score_ks > 0 takes the
+// scored kernel (2-component offsets) with score_hm = the stride-4 heat maps.
+int og_collect_launch(const char *name, const float *scores, const int64_t *inds, int N, int vector_nd, const og_collect::Args &a,
+                      const float *score_hm, int score_ks, void *stream)
 {
-    OG_REQUIRE(scores && inds && a.offs && a.score_hm && a.jf && a.jt && a.limbs, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(a.off_lowres && a.H % 4 == 0 && a.W % 4 == 0, OG_EINVAL, "%s: H,W must be multiples of 4", name);
     OG_REQUIRE((long)a.H * a.W < (1l << 31), OG_EINVAL, "%s: plane too large", name);
     OG_REQUIRE(a.K <= 2048, OG_EUNSUPPORTED, "%s: k=%d too large", name, a.K);
-    hipLaunchKernelGGL(collect_limbs_scored_kernel, dim3(N * a.L), dim3(64), (size_t)((a.K + 3) & ~3) * 16, (hipStream_t)stream, scores,
-                       inds, a);
-    OG_LAUNCH_CHECK(name);
-    return OG_OK;
-}
-
-OG_API int og_collect_limbs_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                                int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                                float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream)
-{
-    return og_collect_limbs_nd_f32(scores, inds, offs, off_is_lowres, 2, N, C, H, W, jf, jt, L, k, thre_hmp, min_len,
-                                   resize_factor, limbs, stream);
-}
-
-OG_API int og_collect_limbs_nd_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                                   int vector_nd, int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L,
-                                   int k, float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream)
-{
-    return og_collect_limbs_ex_f32(scores, inds, offs, off_is_lowres, vector_nd, nullptr, 0, N, C, H, W, jf, jt, L, k,
-                                   thre_hmp, min_len, resize_factor, limbs, stream);
-}
-
-OG_API int og_collect_limbs_ex_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                                   int vector_nd, const float *scales, int scales_mode, int N, int C, int H, int W,
-                                   const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                   float resize_factor, float *limbs, void *stream)
-{
-    return og_collect_limbs_full_f32(scores, inds, offs, off_is_lowres, vector_nd, scales, scales_mode, nullptr, 0, N, C, H, W, jf,
-                                     jt, L, k, thre_hmp, min_len, resize_factor, limbs, stream);
-}
-
-OG_API int og_collect_limbs_full_f32(const float *scores, const int64_t *inds, const float *offs, int off_is_lowres,
-                                     int vector_nd, const float *scales, int scales_mode, const float *jitter,
-                                     int jitter_mode, int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L,
-                                     int k, float thre_hmp, float min_len, float resize_factor, float *limbs, void *stream)
-{
-    const char *name = "og_collect_limbs_full_f32";
-    OG_REQUIRE((jitter_mode == 0 || jitter_mode == 1 || jitter_mode == 3) && (jitter_mode == 0) == (jitter == nullptr),
-               OG_EINVAL, "%s: jitter_mode 0 (no head), 1 (hi-res maps) or 3 (stride-4 maps), with a map exactly when not 0", name);
-    OG_REQUIRE(jitter_mode == 0 || (H == W && vector_nd == 2), OG_EUNSUPPORTED,
-               "%s: the jitter refinement indexes its maps [x][y] like the reference: square inputs, 2-component offsets", name);
-    OG_REQUIRE(jitter_mode != 3 || H % 4 == 0, OG_EINVAL, "%s: H,W must be multiples of 4", name);
-    OG_REQUIRE(scales_mode >= 0 && scales_mode <= 3 && (scales_mode == 0) == (scales == nullptr), OG_EINVAL,
-               "%s: scales_mode 0 (no scale head) .. 3, with a map exactly when it is not 0", name);
-    OG_REQUIRE(scales_mode < 2 || (H % 4 == 0 && W % 4 == 0), OG_EINVAL, "%s: H,W must be multiples of 4", name);
-    OG_REQUIRE(vector_nd == 2 || vector_nd == 4, OG_EUNSUPPORTED, "%s: vector_nd must be 2 or 4", name);
-    OG_REQUIRE(scores && inds && offs && jf && jt && limbs, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && L > 0 && k > 0, OG_EINVAL, "%s: bad shape", name);
-    OG_REQUIRE(!off_is_lowres || (H % 4 == 0 && W % 4 == 0), OG_EINVAL, "%s: H,W must be multiples of 4", name);
-    OG_REQUIRE((long)H * W < (1l << 31), OG_EINVAL, "%s: plane too large", name);
-    OG_REQUIRE(k <= 2048, OG_EUNSUPPORTED, "%s: k=%d too large", name, k);
-    auto kern = vector_nd == 2 ? collect_limbs_kernel<2> : collect_limbs_kernel<4>;
-    const og_collect::Args a{offs, off_is_lowres, C, H, W, jf, jt, L, k, thre_hmp, min_len, resize_factor, scales, scales_mode,
-                             jitter, jitter_mode, limbs};
-    hipLaunchKernelGGL(kern, dim3(N * L), dim3(64), (size_t)((k + 3) & ~3) * 16, (hipStream_t)stream, scores, inds, a);
+    const dim3 grid(N * a.L);
+    const size_t lds = (size_t)((a.K + 3) & ~3) * 16;
+    if (score_ks > 0) {
+        const og_collect::ScoredArgs sa{a, score_hm, score_ks, nullptr};
+        hipLaunchKernelGGL(collect_limbs_scored_kernel, grid, dim3(64), lds, (hipStream_t)stream, scores, inds, sa);
+    } else {
+        auto kern = vector_nd == 2 ? collect_limbs_kernel<2> : collect_limbs_kernel<4>;
+        hipLaunchKernelGGL(kern, grid, dim3(64), lds, (hipStream_t)stream, scores, inds, a);
+    }
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }

@@ -338,7 +338,7 @@ __device__ __forceinline__ void limb_rows(const ArgsT &a, int n, int l, int lane
 
 }  // namespace og_collect
 
-// csrc/collect.hip, for og_generate_limbs_fused*_scored_f32 (csrc/nms_topk.hip) on shapes whose merge-and-pair stage does not fit
-// the LDS: og_collect_limbs_full_f32 with the refined sampling (a.offs = the stride-4 offsets, 2 components).
-int og_collect_limbs_scored_impl(const char *name, const float *scores, const int64_t *inds, int N, const og_collect::ScoredArgs &a,
-                                 void *stream);
+// csrc/collect.hip: the stand-alone pairing launch, for og_collect_limbs_f32 and for og_generate_limbs_f32 on shapes whose
+// merge-and-pair stage does not fit the LDS (both in csrc/nms_topk.hip, next to the descriptor's validation).
+int og_collect_launch(const char *name, const float *scores, const int64_t *inds, int N, int vector_nd, const og_collect::Args &a,
+                      const float *score_hm, int score_ks, void *stream);

@@ -1023,7 +1023,8 @@ struct Pairing {   // og_generate_limbs_f32: the merge launch pairs the limbs as
     const float *score_hm = nullptr;     // scored_off (og_collect::ScoredArgs): score_ks > 0 selects merge_collect_scored_kernel
     int score_ks = 0;
     const int32_t *kp_perm = nullptr;
-    bool flip_heads = false;             // og_collect::FlipHeadsArgs (K1-fused flip form with a scale / jitter pair; kp_perm set)
+    // og_collect::FlipHeadsArgs: the flip fold with a scale / jitter pair (K1-fused only, kp_perm set)
+    bool flip_heads() const { return a.limb_perm && (a.scales || a.jitter); }
 };
 
 template <bool NMS_MODE, bool FUSED = false>
@@ -1085,7 +1086,7 @@ int run_topk(const float *in, long planes, int H, int W, int k, float *out_score
         const size_t plds = 2 * mlds + (size_t)((k + 3) & ~3) * 32;
         if (pair && plds <= kDynLdsLimit) {
             const int NL = pair->N * pair->a.L;
-            if (FUSED && pair->flip_heads) {
+            if (FUSED && pair->flip_heads()) {
                 const dim3 grid((unsigned)(NL + (planes + 1) / 2));
                 if (pair->score_ks > 0) {
                     const og_collect::FlipHeadsArgs<og_collect::ScoredArgs> ha{{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm},
@@ -1194,181 +1195,98 @@ OG_API size_t og_generate_limbs_workspace_bytes(int N, int C, int H, int W, int 
     return two_step_bytes(N, C, H, W, k, true);
 }
 
-// hm_lowres: hmps_hr holds the STRIDE-4 heat maps (N [2N with kp_perm], C, H/4, W/4) and the x4 bicubic runs inside the band kernel
-// (K1-fused); kp_perm (with hm_lowres only): flip-test, the heat maps of [images | mirrored images] merged on the fly.
-static int generate_limbs_impl(const char *name, const float *hmps_hr, const float *offs, int off_is_lowres, int vector_nd,
-                               const float *scales, int scales_mode, const float *jitter, int jitter_mode,
-                               int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                               float thre_hmp, float min_len, float resize_factor, float *topk_scores,
-                               int64_t *topk_inds, float *limbs, const int32_t *limb_perm, const int32_t *reserve_mask,
-                               void *workspace, size_t workspace_bytes, void *stream, bool hm_lowres = false,
-                               const int32_t *kp_perm = nullptr, int score_ks = 0, bool flip_heads = false)
+// The support matrix of OgLimbsDesc: every rule once, for both entry points (`collect`: og_collect_limbs_f32, which takes finished
+// candidate lists -- no top-k stage, no flip fold, heat maps only as the weights of scored_off).
+static int validate_limbs_desc(const char *name, const OgLimbsDesc *d, bool collect)
 {
-    // score_ks > 0 (hm_lowres forms only): scored_off, the offset taps refined from the stride-4 heat maps = hmps_hr itself
-    OG_REQUIRE(score_ks == 0 || (score_ks >= 1 && score_ks <= 7 && score_ks % 2 == 1), OG_EINVAL,
-               "%s: ksize must be odd, 1..7 (got %d)", name, score_ks);
-    OG_REQUIRE(score_ks == 0 || (hm_lowres && off_is_lowres && vector_nd == 2), OG_EUNSUPPORTED,
+    OG_REQUIRE(d, OG_EINVAL, "%s: null pointer", name);
+    OG_REQUIRE(d->size == sizeof(OgLimbsDesc), OG_EINVAL, "%s: descriptor size %u, this library's is %zu", name, d->size, sizeof(OgLimbsDesc));
+    const int H = d->H, W = d->W, k = d->k, ks = d->score_ksize;
+    const bool flip = d->limb_perm || d->reserve_mask, heads = d->scales || d->jitter;
+    // scored_off: the offset taps refined from the stride-4 heat maps = hmps itself
+    OG_REQUIRE(ks == 0 || (ks >= 1 && ks <= 7 && ks % 2 == 1), OG_EINVAL, "%s: ksize must be 0 or odd, 1..7 (got %d)", name, ks);
+    OG_REQUIRE(ks == 0 || (d->hm_lowres && d->off_lowres && d->vector_nd == 2), OG_EUNSUPPORTED,
                "%s: scored offsets need the stride-4 maps and 2-component offsets", name);
-    OG_REQUIRE(hmps_hr && offs && jf && jt && limbs && workspace, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE((topk_scores == nullptr) == (topk_inds == nullptr), OG_EINVAL, "%s: topk_scores and topk_inds go together", name);
-    OG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && L > 0 && k > 0, OG_EINVAL, "%s: bad shape", name);
-    OG_REQUIRE((jitter_mode == 0 || jitter_mode == 1 || jitter_mode == 3) && (jitter_mode == 0) == (jitter == nullptr),
-               OG_EINVAL, "%s: jitter_mode 0 (no head), 1 (hi-res maps) or 3 (stride-4 maps), with a map exactly when not 0", name);
-    OG_REQUIRE(jitter_mode == 0 || (H == W && vector_nd == 2), OG_EUNSUPPORTED,
-               "%s: the jitter refinement indexes its maps [x][y] like the reference: square inputs, 2-component offsets", name);
-    OG_REQUIRE(scales_mode >= 0 && scales_mode <= 3 && (scales_mode == 0) == (scales == nullptr), OG_EINVAL,
+    OG_REQUIRE((d->hmps || (collect && ks == 0)) && d->offs && d->jf && d->jt && d->limbs, OG_EINVAL, "%s: null pointer", name);
+    // the flip fold: offsets (limb_perm + reserve_mask) on their own over hi-res heat maps, or heat maps (kp_perm) and offsets together
+    OG_REQUIRE(!flip || !collect, OG_EUNSUPPORTED, "%s: the flip fold belongs to og_generate_limbs_f32", name);
+    OG_REQUIRE((d->limb_perm == nullptr) == (d->reserve_mask == nullptr), OG_EINVAL,
+               "%s: null pointer (limb_perm and reserve_mask go together)", name);
+    OG_REQUIRE(!flip || (d->off_lowres && d->vector_nd == 2), OG_EUNSUPPORTED,
+               "%s: the flip fold needs the stride-4 offsets and 2 components", name);
+    OG_REQUIRE(!d->kp_perm || d->hm_lowres, OG_EUNSUPPORTED, "%s: kp_perm folds the stride-4 heat maps (hm_lowres)", name);
+    OG_REQUIRE(!d->hm_lowres || (d->kp_perm != nullptr) == flip, OG_EINVAL,
+               "%s: null pointer (on the stride-4 heat maps kp_perm and limb_perm go together)", name);
+    OG_REQUIRE(!(flip && heads) || d->hm_lowres, OG_EUNSUPPORTED, "%s: the flip fold takes a scale / jitter pair only with hm_lowres", name);
+    OG_REQUIRE(collect || (d->topk_scores == nullptr) == (d->topk_inds == nullptr), OG_EINVAL,
+               "%s: topk_scores and topk_inds go together", name);
+    OG_REQUIRE(d->N > 0 && d->C > 0 && H > 0 && W > 0 && d->L > 0 && k > 0, OG_EINVAL, "%s: bad shape", name);
+    // the optional heads
+    OG_REQUIRE(d->scales_mode >= 0 && d->scales_mode <= 3 && (d->scales_mode == 0) == (d->scales == nullptr), OG_EINVAL,
                "%s: scales_mode 0 (no scale head) .. 3, with a map exactly when it is not 0", name);
-    OG_REQUIRE(vector_nd == 2 || vector_nd == 4, OG_EUNSUPPORTED, "%s: vector_nd must be 2 or 4", name);
-    OG_REQUIRE(!(off_is_lowres || scales_mode >= 2 || jitter_mode == 3) || (H % 4 == 0 && W % 4 == 0), OG_EINVAL,
+    OG_REQUIRE((d->jitter_mode == 0 || d->jitter_mode == 1 || d->jitter_mode == 3) && (d->jitter_mode == 0) == (d->jitter == nullptr),
+               OG_EINVAL, "%s: jitter_mode 0 (no head), 1 (hi-res maps) or 3 (stride-4 maps), with a map exactly when not 0", name);
+    OG_REQUIRE(!d->hm_lowres || d->scales_mode != 1, OG_EINVAL,
+               "%s: with hm_lowres the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
+    OG_REQUIRE(!d->hm_lowres || d->jitter_mode != 1, OG_EINVAL,
+               "%s: with hm_lowres the jitter maps are the stride-4 head output (jitter_mode 3)", name);
+    OG_REQUIRE(d->jitter_mode == 0 || (H == W && d->vector_nd == 2), OG_EUNSUPPORTED,
+               "%s: the jitter refinement indexes its maps [x][y] like the reference: square inputs, 2-component offsets", name);
+    OG_REQUIRE(d->vector_nd == 2 || d->vector_nd == 4, OG_EUNSUPPORTED, "%s: vector_nd must be 2 or 4", name);
+    // sizes
+    OG_REQUIRE(!(d->hm_lowres || d->off_lowres || d->scales_mode >= 2 || d->jitter_mode == 3) || (H % 4 == 0 && W % 4 == 0), OG_EINVAL,
                "%s: H,W must be multiples of 4", name);
-    OG_REQUIRE((long)H * W >= k, OG_EINVAL, "%s: selected index k out of range (k=%d > H*W=%ld)", name, k, (long)H * W);
-    OG_REQUIRE(2l * (H + W) - 4 >= k, OG_EINVAL, "%s: plane border smaller than k", name);
+    OG_REQUIRE(!d->hm_lowres || (H / 4 < (1 << 14) && W / 4 < (1 << 14)), OG_EINVAL, "%s: bad shape", name);
+    if (!collect) {
+        OG_REQUIRE((long)H * W >= k, OG_EINVAL, "%s: selected index k out of range (k=%d > H*W=%ld)", name, k, (long)H * W);
+        OG_REQUIRE(2l * (H + W) - 4 >= k, OG_EINVAL, "%s: plane border smaller than k", name);
+    }
+    return OG_OK;
+}
+
+static og_collect::Args collect_args(const OgLimbsDesc *d)
+{
+    og_collect::Args a{d->offs, d->off_lowres, d->C, d->H, d->W, d->jf, d->jt, d->L, d->k, d->thre_hmp, d->min_len, d->resize_factor,
+                       d->scales, d->scales_mode, d->jitter, d->jitter_mode, d->limbs};
+    if (d->limb_perm) { a.limb_perm = d->limb_perm; a.reserve = d->reserve_mask; a.flip_N = d->N; }
+    return a;
+}
+
+OG_API int og_collect_limbs_f32(const float *scores, const int64_t *inds, const OgLimbsDesc *d, void *stream)
+{
+    const char *name = "og_collect_limbs_f32";
+    if (const int rc = validate_limbs_desc(name, d, true)) return rc;
+    OG_REQUIRE(scores && inds, OG_EINVAL, "%s: null pointer", name);
+    return og_collect_launch(name, scores, inds, d->N, d->vector_nd, collect_args(d), d->hmps, d->score_ksize, stream);
+}
+
+OG_API int og_generate_limbs_f32(const OgLimbsDesc *d, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "og_generate_limbs_f32";
+    if (const int rc = validate_limbs_desc(name, d, false)) return rc;
+    OG_REQUIRE(workspace, OG_EINVAL, "%s: null pointer", name);
     OG_REQUIRE((uintptr_t)workspace % 16 == 0, OG_EINVAL, "%s: workspace must be 16-byte aligned", name);
-    og_collect::Args ca{offs, off_is_lowres, C, H, W, jf, jt, L, k, thre_hmp, min_len, resize_factor, scales, scales_mode,
-                        jitter, jitter_mode, limbs};
-    if (limb_perm) { ca.limb_perm = limb_perm; ca.reserve = reserve_mask; ca.flip_N = N; }
+    const int N = d->N, C = d->C, H = d->H, W = d->W, k = d->k;
+    const og_collect::Args ca = collect_args(d);
     // band top-k, then ONE launch that merges the band lists and pairs the limbs
-    const bool own_lists = topk_scores == nullptr;
+    const bool own_lists = d->topk_scores == nullptr;
     const size_t need = two_step_bytes(N, C, H, W, k, own_lists);
     OG_REQUIRE(need != 0, OG_EUNSUPPORTED, "%s: unsupported W=%d or k=%d", name, W, k);
     OG_REQUIRE(workspace_bytes >= need, OG_ENOSPC, "%s: workspace %zu < %zu", name, workspace_bytes, need);
     char *ws2 = (char *)workspace + kP2TicketBytes;
     const size_t topk = og_align_up(og_topk_workspace_bytes((long)N * C, H, W, k), 256);
-    float *sc = own_lists ? reinterpret_cast<float *>(ws2 + topk + (size_t)N * C * k * 8) : topk_scores;
-    int64_t *id = own_lists ? reinterpret_cast<int64_t *>(ws2 + topk) : topk_inds;
-    const Pairing pr{ca, vector_nd, N, score_ks > 0 ? hmps_hr : nullptr, score_ks, kp_perm, flip_heads};
+    float *sc = own_lists ? reinterpret_cast<float *>(ws2 + topk + (size_t)N * C * k * 8) : d->topk_scores;
+    int64_t *id = own_lists ? reinterpret_cast<int64_t *>(ws2 + topk) : d->topk_inds;
+    const Pairing pr{ca, d->vector_nd, N, d->score_ksize > 0 ? d->hmps : nullptr, d->score_ksize, d->kp_perm};
     const bool can_pair = (long)H * W < (1l << 31) && k <= 2048;
-    OG_REQUIRE(!hm_lowres || (H % 4 == 0 && W % 4 == 0), OG_EINVAL, "%s: H,W must be multiples of 4", name);
-    const int rc = hm_lowres ? run_topk<true, true>(hmps_hr, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
-                                                    can_pair ? &pr : nullptr, FlipSrc{kp_perm, N, C})
-                             : run_topk<true>(hmps_hr, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
-                                              can_pair ? &pr : nullptr);
+    const int rc = d->hm_lowres ? run_topk<true, true>(d->hmps, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
+                                                       can_pair ? &pr : nullptr, FlipSrc{d->kp_perm, N, C})
+                                : run_topk<true>(d->hmps, (long)N * C, H, W, k, sc, id, ws2, topk, (hipStream_t)stream, name,
+                                                 can_pair ? &pr : nullptr);
     if (rc < 0 || rc == 1) return rc < 0 ? rc : OG_OK;
     // (shapes whose merge + pairing stage does not fit the LDS: the lists are complete, pair them with the collect kernel)
-    OG_REQUIRE(!limb_perm, OG_EUNSUPPORTED, "%s: k = %d is too large for the merge-and-pair stage of the flip-folded form", name, k);
-    if (score_ks > 0)
-        return og_collect_limbs_scored_impl(name, sc, id, N, og_collect::ScoredArgs{ca, hmps_hr, score_ks, nullptr}, stream);
-    return og_collect_limbs_full_f32(sc, id, offs, off_is_lowres, vector_nd, scales, scales_mode, jitter, jitter_mode, N, C,
-                                     H, W, jf, jt, L, k, thre_hmp, min_len, resize_factor, limbs, stream);
-}
-
-OG_API int og_generate_limbs_f32(const float *hmps_hr, const float *offs, int off_is_lowres, int vector_nd,
-                                 const float *scales, int scales_mode, const float *jitter, int jitter_mode,
-                                 int N, int C, int H, int W, const int32_t *jf, const int32_t *jt, int L, int k,
-                                 float thre_hmp, float min_len, float resize_factor, float *topk_scores,
-                                 int64_t *topk_inds, float *limbs, int flags, void *workspace, size_t workspace_bytes, void *stream)
-{
-    (void)flags;    // reserved (the one-launch forms of rounds 2 / 3 were selected here): pass 0
-    return generate_limbs_impl("og_generate_limbs_f32", hmps_hr, offs, off_is_lowres, vector_nd, scales, scales_mode, jitter,
-                               jitter_mode, N, C, H, W, jf, jt, L, k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds,
-                               limbs, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-// generate_limbs with flip_augment's OFFSET merge (decoder/factory.py:129-138) folded into the offset sampling: offs_pair is the
-// stride-4 offset head output for [images | mirrored images], (2N, 2L, H/4, W/4)
-OG_API int og_generate_limbs_flip_f32(const float *hmps_hr, const float *offs_pair, const int32_t *limb_perm,
-                                      const int32_t *reserve_mask, int N, int C, int H, int W, const int32_t *jf,
-                                      const int32_t *jt, int L, int k, float thre_hmp, float min_len, float resize_factor,
-                                      float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace,
-                                      size_t workspace_bytes, void *stream)
-{
-    const char *name = "og_generate_limbs_flip_f32";
-    OG_REQUIRE(limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
-    return generate_limbs_impl(name, hmps_hr, offs_pair, 1, 2, nullptr, 0, nullptr, 0, N, C, H, W, jf, jt, L, k, thre_hmp, min_len,
-                               resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace, workspace_bytes,
-                               stream);
-}
-
-// ---- K1-fused: generate_limbs straight from the STRIDE-4 head outputs.  The x4 bicubic of decoder/factory.py:74-75 runs inside the
-// band kernel (bit-identical to og_upsample_bicubic4_f32), the offsets / scale / jitter maps are sampled at the peaks: neither hi-res
-// tensor exists.  Two launches, as og_generate_limbs_f32.
-OG_API int og_generate_limbs_fused_f32(const float *hmps_lr, const float *offs_lr, int vector_nd, const float *scales_lr,
-                                       int scales_mode, const float *jitter_lr, int jitter_mode, int N, int C, int h, int w,
-                                       const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                       float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs, void *workspace,
-                                       size_t workspace_bytes, void *stream)
-{
-    const char *name = "og_generate_limbs_fused_f32";
-    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
-    OG_REQUIRE(scales_mode == 0 || scales_mode >= 2, OG_EINVAL, "%s: the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
-    OG_REQUIRE(jitter_mode == 0 || jitter_mode == 3, OG_EINVAL, "%s: the jitter maps are the stride-4 head output (jitter_mode 3)", name);
-    return generate_limbs_impl(name, hmps_lr, offs_lr, 1, vector_nd, scales_lr, scales_mode, jitter_lr, jitter_mode, N, C, 4 * h, 4 * w,
-                               jf, jt, L, k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds, limbs, nullptr, nullptr, workspace,
-                               workspace_bytes, stream, true);
-}
-
-// ... with flip_augment (decoder/factory.py:98-146, the averaged form) folded into BOTH consumers: hm_pair_lr (2N,C,h,w) and
-// offs_pair_lr (2N,2L,h,w) are the head outputs for [images | mirrored images]; no merge pass, no hi-res tensor.
-OG_API int og_generate_limbs_fused_flip_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                            const int32_t *limb_perm, const int32_t *reserve_mask, int N, int C, int h, int w,
-                                            const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                            float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
-                                            void *workspace, size_t workspace_bytes, void *stream)
-{
-    const char *name = "og_generate_limbs_fused_flip_f32";
-    OG_REQUIRE(kp_perm && limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
-    return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, nullptr, 0, nullptr, 0, N, C, 4 * h, 4 * w, jf, jt, L, k, thre_hmp,
-                               min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace,
-                               workspace_bytes, stream, true, kp_perm);
-}
-
-// ---- scored_off inside the pairing: the two K1-fused forms with every offset tap refined on the spot (og_collect::ScoredArgs,
-// collect_body.h) from the stride-4 heat maps they already take; bit-identical to og_scored_offset_f32 (after og_flip_merge_f32,
-// for the flip form) in front of the unrefined entry point.
-OG_API int og_generate_limbs_fused_scored_f32(const float *hmps_lr, const float *offs_lr, int ksize, const float *scales_lr,
-                                              int scales_mode, const float *jitter_lr, int jitter_mode, int N, int C, int h, int w,
-                                              const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp, float min_len,
-                                              float resize_factor, float *topk_scores, int64_t *topk_inds, float *limbs,
-                                              void *workspace, size_t workspace_bytes, void *stream)
-{
-    const char *name = "og_generate_limbs_fused_scored_f32";
-    OG_REQUIRE(ksize >= 1 && ksize <= 7 && ksize % 2 == 1, OG_EINVAL, "%s: ksize must be odd, 1..7 (got %d)", name, ksize);
-    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
-    OG_REQUIRE(scales_mode == 0 || scales_mode >= 2, OG_EINVAL, "%s: the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
-    OG_REQUIRE(jitter_mode == 0 || jitter_mode == 3, OG_EINVAL, "%s: the jitter maps are the stride-4 head output (jitter_mode 3)", name);
-    return generate_limbs_impl(name, hmps_lr, offs_lr, 1, 2, scales_lr, scales_mode, jitter_lr, jitter_mode, N, C, 4 * h, 4 * w, jf, jt, L,
-                               k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds, limbs, nullptr, nullptr, workspace,
-                               workspace_bytes, stream, true, nullptr, ksize);
-}
-
-OG_API int og_generate_limbs_fused_flip_scored_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                                   const int32_t *limb_perm, const int32_t *reserve_mask, int ksize, int N, int C,
-                                                   int h, int w, const int32_t *jf, const int32_t *jt, int L, int k, float thre_hmp,
-                                                   float min_len, float resize_factor, float *topk_scores, int64_t *topk_inds,
-                                                   float *limbs, void *workspace, size_t workspace_bytes, void *stream)
-{
-    const char *name = "og_generate_limbs_fused_flip_scored_f32";
-    OG_REQUIRE(ksize >= 1 && ksize <= 7 && ksize % 2 == 1, OG_EINVAL, "%s: ksize must be odd, 1..7 (got %d)", name, ksize);
-    OG_REQUIRE(kp_perm && limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
-    return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, nullptr, 0, nullptr, 0, N, C, 4 * h, 4 * w, jf, jt, L, k, thre_hmp,
-                               min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm, reserve_mask, workspace,
-                               workspace_bytes, stream, true, kp_perm, ksize);
-}
-
-// ---- the flip form with the optional heads: the scale pair (2N,C,h,w) and / or the jitter pair (2N,2,h,w) of [images | mirrored
-// images] sampled at the peaks as og_flip_merge_heads_f32 would have merged them (og_collect::FlipHeadsArgs); ksize 0 = unrefined
-// offsets, odd 1..7 = scored_off.  Bit-identical to og_flip_merge_f32 + og_flip_merge_heads_f32 + og_generate_limbs_fused[_scored]_f32.
-OG_API int og_generate_limbs_fused_flip_heads_f32(const float *hm_pair_lr, const int32_t *kp_perm, const float *offs_pair_lr,
-                                                  const int32_t *limb_perm, const int32_t *reserve_mask, int ksize,
-                                                  const float *scales_pair_lr, int scales_mode, const float *jitter_pair_lr,
-                                                  int jitter_mode, int N, int C, int h, int w, const int32_t *jf, const int32_t *jt,
-                                                  int L, int k, float thre_hmp, float min_len, float resize_factor, float *topk_scores,
-                                                  int64_t *topk_inds, float *limbs, void *workspace, size_t workspace_bytes,
-                                                  void *stream)
-{
-    const char *name = "og_generate_limbs_fused_flip_heads_f32";
-    OG_REQUIRE(ksize == 0 || (ksize >= 1 && ksize <= 7 && ksize % 2 == 1), OG_EINVAL, "%s: ksize must be 0 or odd, 1..7 (got %d)", name,
-               ksize);
-    OG_REQUIRE(kp_perm && limb_perm && reserve_mask, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(scales_pair_lr || jitter_pair_lr, OG_EINVAL, "%s: null pointer (neither head given: og_generate_limbs_fused_flip_f32)", name);
-    OG_REQUIRE(h > 0 && w > 0 && h < (1 << 14) && w < (1 << 14), OG_EINVAL, "%s: bad shape", name);
-    OG_REQUIRE(scales_mode == 0 || scales_mode >= 2, OG_EINVAL, "%s: the scale maps are the stride-4 head output (scales_mode 2 / 3)", name);
-    OG_REQUIRE(jitter_mode == 0 || jitter_mode == 3, OG_EINVAL, "%s: the jitter maps are the stride-4 head output (jitter_mode 3)", name);
-    return generate_limbs_impl(name, hm_pair_lr, offs_pair_lr, 1, 2, scales_pair_lr, scales_mode, jitter_pair_lr, jitter_mode, N, C, 4 * h,
-                               4 * w, jf, jt, L, k, thre_hmp, min_len, resize_factor, topk_scores, topk_inds, limbs, limb_perm,
-                               reserve_mask, workspace, workspace_bytes, stream, true, kp_perm, ksize, true);
+    OG_REQUIRE(!d->limb_perm, OG_EUNSUPPORTED, "%s: k = %d is too large for the merge-and-pair stage of the flip-folded form", name, k);
+    return og_collect_launch(name, sc, id, N, d->vector_nd, ca, d->hmps, d->score_ksize, stream);
 }
 
 #ifdef OG_K1_STAMPS

@@ -22,7 +22,7 @@ class LimbsCollect(object):
 
     The whole of generate_limbs -- NMS, top-k and the pairing -- is ONE C call: two launches queued back to back (band
     top-k; merge + pairing), on hi-res heatmaps (og_generate_limbs_f32) or straight on the stride-4 head output with the x4
-    bicubic inside the band kernel (og_generate_limbs_fused_f32, the production path).
+    bicubic inside the band kernel (hm_lowres in the call's descriptor: K1-fused, the production path).
     """
 
     def __init__(self, hmp_s, off_s, *, topk=40, thre_hmp=0.08, min_len=3,
@@ -40,6 +40,7 @@ class LimbsCollect(object):
         self.include_scale = include_scale
         self.use_jitter_offset = use_jitter_offset
         self.jtypes_f, self.jtypes_t = self.pack_jtypes(skeleton)
+        self._desc_const = {}   # the constant part of the C call's descriptor per device and setting (_call)
         LOG.info('%d limbs, keypoint threshold %.4f, offset/heatmap unit ratio %.3f',
                  len(skeleton), thre_hmp, self.resize_factor)
 
@@ -78,65 +79,34 @@ class LimbsCollect(object):
         hmps_hr = _lib.require_device(hmps_hr, 'hmps_hr')
         offs = _lib.require_device(offs_pair_lr, 'offs')
         n, c, h, w = hmps_hr.shape
-        n_limbs = len(self.skeleton)
-        assert tuple(offs.shape) == (2 * n, 2 * n_limbs, h // 4, w // 4), 'offsets of [images | mirrored images] at stride 4'
-        dev, lib = hmps_hr.device, _lib.load()
-        limbs = torch.empty((n, n_limbs, self.K, 13), dtype=torch.float32, device=dev)
-        jf, jt = _lib.int_table(self.jtypes_f, dev), _lib.int_table(self.jtypes_t, dev)
-        with _lib.stage_timer('k1_generate_limbs', dev):
-            ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, h, w, self.K), 'limbs')   # zero-filled
-            _lib.check(lib.og_generate_limbs_flip_f32(
-                _lib.ptr(hmps_hr), _lib.ptr(offs), _lib.ptr(_lib.int_table(limb_perm, dev)), _lib.ptr(_lib.int_table(reserve_mask, dev)),
-                n, c, h, w, _lib.ptr(jf), _lib.ptr(jt), n_limbs, self.K, float(self.thre_hmp), float(self.min_len),
-                float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
-        return limbs
+        assert tuple(offs.shape) == (2 * n, 2 * len(self.skeleton), h // 4, w // 4), 'offsets of [images | mirrored images] at stride 4'
+        dev = hmps_hr.device
+        return self._call('k1_generate_limbs', hmps_hr, offs, (n, c, h, w), off_lowres=1, vector_nd=2,
+                          limb_perm=_lib.int_table(limb_perm, dev), reserve_mask=_lib.int_table(reserve_mask, dev))
 
     def generate_limbs_fused_flip(self, hm_pair_lr, offs_pair_lr, kp_perm, limb_perm, reserve_mask, scored_ks=0, scmps_pair_lr=None,
                                   scale_inter='bicubic', jomps_pair_lr=None):
-        """generate_limbs_fused on the flip-merged maps WITHOUT merging them first (og_generate_limbs_fused_flip_f32): the stride-4
+        """generate_limbs_fused on the flip-merged maps WITHOUT merging them first (LimbsDesc.kp_perm / limb_perm): the stride-4
         head outputs of [images | mirrored images], (2N, C, h, w) and (2N, 2L, h, w); every heat-map source value and every offset tap
         is computed as PostProcess.flip_augment would have written it (decoder/factory.py:98-146).  2-component offsets.  scored_ks > 0:
-        scored_off with that window, every offset tap refined inside the pairing (og_generate_limbs_fused_flip_scored_f32); 0 = the
-        unrefined call.  scmps_pair_lr (2N, C, h, w) / jomps_pair_lr (2N, 2, h, w): the keypoint-scale / jitter head outputs of the
-        same pairs, sampled at the peaks as flip_augment would have merged them (og_generate_limbs_fused_flip_heads_f32; the
-        jitter maps act under the conditions of _jitter and need square inputs, as everywhere)."""
+        scored_off with that window, every offset tap refined inside the pairing (LimbsDesc.score_ksize); 0 = the unrefined call.
+        scmps_pair_lr (2N, C, h, w) / jomps_pair_lr (2N, 2, h, w): the keypoint-scale / jitter head outputs of the same pairs, sampled
+        at the peaks as flip_augment would have merged them (the jitter maps act under the conditions of _jitter and need square
+        inputs, as everywhere)."""
         hm = _lib.require_device(hm_pair_lr, 'hmps')
         offs = _lib.require_device(offs_pair_lr, 'offs')
         n2, c, h, w = hm.shape
-        n, n_limbs = n2 // 2, len(self.skeleton)
-        assert n2 == 2 * n and tuple(offs.shape) == (n2, 2 * n_limbs, h, w), 'head outputs of [images | mirrored images] at stride 4'
-        dev, lib = hm.device, _lib.load()
-        scl = jit = None
-        if scmps_pair_lr is not None:
-            scl = _lib.require_device(scmps_pair_lr, 'scmps')
-            assert tuple(scl.shape) == (n2, c, h, w), f'scale maps {tuple(scl.shape)}, expected {(n2, c, h, w)}'
-        if self._jitter(jomps_pair_lr) is not None:
-            jit = _lib.require_device(jomps_pair_lr, 'jomps')
-            assert tuple(jit.shape) == (n2, 2, h, w), f'jitter maps {tuple(jit.shape)}, expected {(n2, 2, h, w)}'
-            if h != w:   # the reference indexes the refinement maps [x][y] (collect.py:158-165)
-                raise NotImplementedError('the jitter-offset head needs square inputs (the reference indexes its maps [x][y])')
-        limbs = torch.empty((n, n_limbs, self.K, 13), dtype=torch.float32, device=dev)
-        jf, jt = _lib.int_table(self.jtypes_f, dev), _lib.int_table(self.jtypes_t, dev)
-        with _lib.stage_timer('k1f_fused_limbs', dev):
-            ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, 4 * h, 4 * w, self.K), 'limbs')   # zero-filled
-            tables = (_lib.ptr(hm), _lib.ptr(_lib.int_table(kp_perm, dev)), _lib.ptr(offs), _lib.ptr(_lib.int_table(limb_perm, dev)),
-                      _lib.ptr(_lib.int_table(reserve_mask, dev)))
-            rest = (n, c, h, w, _lib.ptr(jf), _lib.ptr(jt), n_limbs, self.K, float(self.thre_hmp), float(self.min_len),
-                    float(self.resize_factor), None, None, _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-            if scl is not None or jit is not None:
-                heads = (_lib.ptr(scl) if scl is not None else None, (2 if scale_inter == 'bicubic' else 3) if scl is not None else 0,
-                         _lib.ptr(jit) if jit is not None else None, 3 if jit is not None else 0)
-                _lib.check(lib.og_generate_limbs_fused_flip_heads_f32(*tables, int(scored_ks), *heads, *rest), lib)
-            elif scored_ks:
-                _lib.check(lib.og_generate_limbs_fused_flip_scored_f32(*tables, int(scored_ks), *rest), lib)
-            else:
-                _lib.check(lib.og_generate_limbs_fused_flip_f32(*tables, *rest), lib)
-        return limbs
+        n, dev = n2 // 2, hm.device
+        assert n2 == 2 * n and tuple(offs.shape) == (n2, 2 * len(self.skeleton), h, w), 'head outputs of [images | mirrored images] at stride 4'
+        scl, jit = self._heads(scmps_pair_lr, 2 if scale_inter == 'bicubic' else 3, self._jitter(jomps_pair_lr), 3, (n2, c, 4 * h, 4 * w))
+        return self._call('k1f_fused_limbs', hm, offs, (n, c, 4 * h, 4 * w), hm_lowres=1, off_lowres=1, vector_nd=2,
+                          kp_perm=_lib.int_table(kp_perm, dev), limb_perm=_lib.int_table(limb_perm, dev),
+                          reserve_mask=_lib.int_table(reserve_mask, dev), score_ksize=int(scored_ks), **scl, **jit)
 
     def generate_limbs_fused(self, hmps_lr, offs_lr, vector_nd=2, scmps_lr=None, scale_inter='bicubic', jomps_lr=None, scored_ks=0):
         """Same limbs as generate_limbs(F.interpolate(hmps_lr, x4, 'bicubic'), [], F.interpolate(offs_lr, x4,
         'bilinear'), []) with NEITHER hi-res tensor built: K1-fused upsamples inside the NMS kernel.  scored_ks > 0: scored_off
-        with that window, every offset tap refined inside the pairing (og_generate_limbs_fused_scored_f32); 0 = the unrefined call."""
+        with that window, every offset tap refined inside the pairing (LimbsDesc.score_ksize); 0 = the unrefined call."""
         assert hmps_lr.shape[-2:] == offs_lr.shape[-2:], 'spatial resolution should be equal'
         if scored_ks and vector_nd != 2:
             raise NotImplementedError('scored_off needs 2-component offsets (the reference fails here as well)')
@@ -151,48 +121,52 @@ class LimbsCollect(object):
         n, c, h, w = hmps_hr.shape
         if hm_is_lowres:
             h, w = 4 * h, 4 * w
-        n_limbs = len(self.skeleton)
         # cat_flip_offs hands the 4-component offsets on as a (2N, 2L, h, w) view (decoder/factory.py:127);
         # like collect.py:73 only the memory order (N, L, vector_nd, h, w) matters
-        assert offs.numel() == n * vector_nd * n_limbs * offs.shape[-2] * offs.shape[-1], \
+        assert offs.numel() == n * vector_nd * len(self.skeleton) * offs.shape[-2] * offs.shape[-1], \
             'offset channels must be vector_nd x number of limbs'
-        dev = hmps_hr.device
-        lib = _lib.load()
-        if scales is None:
-            scales_mode = 0
-        else:  # keypoint-scale head (collect.py:111-122): maps at input resolution (mode 1) or the stride-4 head output
+        scl, jit = self._heads(scales, scales_mode, jitter, jitter_mode, (n, c, h, w))
+        # one bracket round the whole generate_limbs boundary (K1 + K2): what bench.py prices as "K1"; K1-fused: the x4 bicubic runs
+        # inside the NMS kernel
+        return self._call('k1f_fused_limbs' if hm_is_lowres else 'k1_generate_limbs', hmps_hr, offs, (n, c, h, w),
+                          hm_lowres=int(hm_is_lowres), off_lowres=int(off_is_lowres), vector_nd=int(vector_nd),
+                          score_ksize=int(scored_ks), **scl, **jit)
+
+    @staticmethod
+    def _heads(scales, scales_mode, jitter, jitter_mode, nchw):
+        """The optional heads as LimbsDesc fields ({} = head absent): maps at input resolution (mode 1) or the stride-4 head output."""
+        n, c, h, w = nchw
+        scl = jit = {}
+        if scales is not None:   # keypoint-scale head (collect.py:111-122)
             scales = _lib.require_device(scales, 'scmps')
             expect = (n, c, h, w) if scales_mode == 1 else (n, c, h // 4, w // 4)
             assert tuple(scales.shape) == expect, f'scale maps {tuple(scales.shape)}, expected {expect}'
-        if jitter is None:
-            jitter_mode = 0
-        else:  # jitter-offset head: two shared channels at input resolution (mode 1) or the stride-4 head output
+            scl = dict(scales=scales, scales_mode=int(scales_mode))
+        if jitter is not None:   # jitter-offset head: two shared channels
             jitter = _lib.require_device(jitter, 'jomps')
             expect = (n, 2, h, w) if jitter_mode == 1 else (n, 2, h // 4, w // 4)
             assert tuple(jitter.shape) == expect, f'jitter maps {tuple(jitter.shape)}, expected {expect}'
-        if jitter is not None and h != w:   # the reference indexes the refinement maps [x][y] (collect.py:158-165)
-            raise NotImplementedError('the jitter-offset head needs square inputs (the reference indexes its maps [x][y])')
-        limbs = torch.empty((n, n_limbs, self.K, 13), dtype=torch.float32, device=dev)
-        jf, jt = _lib.int_table(self.jtypes_f, dev), _lib.int_table(self.jtypes_t, dev)
-        # one bracket round the whole generate_limbs boundary (K1 + K2): what bench.py prices as "K1"
-        with _lib.stage_timer('k1f_fused_limbs' if hm_is_lowres else 'k1_generate_limbs', dev):
-            if not hm_is_lowres:
-                ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, h, w, self.K), 'limbs')   # zero-filled
-                _lib.check(lib.og_generate_limbs_f32(
-                    _lib.ptr(hmps_hr), _lib.ptr(offs), int(off_is_lowres), int(vector_nd),
-                    _lib.ptr(scales) if scales is not None else None, int(scales_mode),
-                    _lib.ptr(jitter) if jitter is not None else None, int(jitter_mode), n, c, h, w, _lib.ptr(jf), _lib.ptr(jt),
-                    n_limbs, self.K, float(self.thre_hmp), float(self.min_len), float(self.resize_factor), None, None,
-                    _lib.ptr(limbs), 0, _lib.ptr(ws), ws.numel(),
-                    _lib.stream_ptr(dev)), lib)
-                return limbs
-            # K1-fused: the x4 bicubic runs inside the NMS kernel; ONE C call = two launches (band top-k; merge + pairing)
-            ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(n, c, h, w, self.K), 'limbs')   # zero-filled
-            # (the scored form takes the window where the unrefined one takes vector_nd: its offsets have 2 components)
-            entry = lib.og_generate_limbs_fused_scored_f32 if scored_ks else lib.og_generate_limbs_fused_f32
-            _lib.check(entry(
-                _lib.ptr(hmps_hr), _lib.ptr(offs), int(scored_ks or vector_nd), _lib.ptr(scales) if scales is not None else None, int(scales_mode),
-                _lib.ptr(jitter) if jitter is not None else None, int(jitter_mode), n, c, h // 4, w // 4, _lib.ptr(jf), _lib.ptr(jt),
-                n_limbs, self.K, float(self.thre_hmp), float(self.min_len), float(self.resize_factor), None, None,
-                _lib.ptr(limbs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
+            if h != w:   # the reference indexes the refinement maps [x][y] (collect.py:158-165)
+                raise NotImplementedError('the jitter-offset head needs square inputs (the reference indexes its maps [x][y])')
+            jit = dict(jitter=jitter, jitter_mode=int(jitter_mode))
+        return scl, jit
+
+    def _call(self, timer, hmps, offs, nchw, **form):
+        """ONE og_generate_limbs_f32 call = two launches (band top-k; merge + pairing): nchw = images, joint channels and the INPUT
+        resolution; form = the LimbsDesc fields that tell the forms apart (tensors for pointers).  The descriptor is a copy of the
+        cached constant part with this call's fields written over it: the host path of the decoder's hot call."""
+        dev, lib = hmps.device, _lib.load()
+        const = (dev.index, len(self.skeleton), self.K, self.thre_hmp, self.min_len, self.resize_factor)
+        if const not in self._desc_const:
+            self._desc_const[const] = _lib.LimbsDesc(jf=_lib.int_table(self.jtypes_f, dev), jt=_lib.int_table(self.jtypes_t, dev),
+                                                     **dict(zip(('L', 'k', 'thre_hmp', 'min_len', 'resize_factor'), const[1:])))
+        desc = _lib.LimbsDesc.from_buffer_copy(self._desc_const[const])
+        limbs = torch.empty((nchw[0], desc.L, desc.k, 13), dtype=torch.float32, device=dev)
+        desc.N, desc.C, desc.H, desc.W = nchw
+        desc.hmps, desc.offs, desc.limbs = hmps.data_ptr(), offs.data_ptr(), limbs.data_ptr()
+        for name, v in form.items():    # an int, or a tensor for its pointer
+            setattr(desc, name, v if type(v) is int else v.data_ptr())
+        with _lib.stage_timer(timer, dev):
+            ws = _lib.workspace(dev, lib.og_generate_limbs_workspace_bytes(*nchw, desc.k), 'limbs')   # zero-filled
+            _lib.check(lib.og_generate_limbs_f32(desc, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
         return limbs

@@ -141,7 +141,7 @@ class PostProcess(torch.nn.Module):
         self.fused_upsample = os.environ.get('OG_FUSED_UPSAMPLE', '1') != '0'
         # flip-test (2-component offsets): flip_augment's merge rides on the loads of K1a and on the offset sampling of K1 instead of
         # running as its own pass (K0, og_flip_merge_f32); identical results.  With K1-fused the keypoint-scale / jitter heads are
-        # sampled from their pairs the same way (og_generate_limbs_fused_flip_heads_f32)
+        # sampled from their pairs the same way (the same call with the scale / jitter pairs in its descriptor)
         self.fold_flip = os.environ.get('OG_FOLD_FLIP', '1') != '0'
         # scored_off: the window of the heatmap-weighted offset refinement (the reference hard-codes 3 at its call site,
         # decoder/factory.py:70-72).  K1-fused refines every offset tap inside the pairing; fused_upsample=False runs
@@ -265,7 +265,7 @@ class PostProcess(torch.nn.Module):
                     # merge + pairing of the folded form keeps a plane's lists in LDS: beyond k ~ 226 at 640 x 640 (half that for inputs
                     # twice as tall) it does not fit and the C side says OG_EUNSUPPORTED.  The unfolded route below (flip_augment as its own
                     # pass, then K1-fused with its collect-kernel fallback) serves the same request with the same results.
-                    if f'(code {_lib.OG_EUNSUPPORTED})' not in str(e):
+                    if e.code != _lib.OG_EUNSUPPORTED:
                         raise
             else:
                 hmps_hr = upsample4_flip(hmps, self.keypoints_flips)

@@ -2,7 +2,7 @@
 
 Off by default in the reference (`scored_off=False`, decoder/factory.py:52; evaluate.py never enables it).  On the device it is HIP
 like every other decoder stage: `PostProcess(scored_off=True)` refines every offset tap INSIDE the pairing kernel
-(og_generate_limbs_fused_scored_f32 / ..._flip_scored_f32: the refined tensor is never built), and the public function
+(og_generate_limbs_f32 with score_ksize in its descriptor: the refined tensor is never built), and the public function
 `scored_offset` on device tensors is one launch of og_scored_offset_f32 (csrc/scored_offset.hip).  Both are bit-identical to the
 torch-CPU formulation below, which stays for CPU tensors only: tests/test_oracle_golden.py and tools/gen_golden.py use it as the
 witness of equality with the imported reference.  It is not a fallback of the decoder -- PostProcess still refuses CPU features.

@@ -22,6 +22,24 @@ def test_header_and_binding_agree():
     assert declared_symbols() == sorted(_lib.SIGNATURES)
 
 
+def test_limbs_descriptor_mirrors_the_header():
+    """OgLimbsDesc field for field, in order; its `size` is the only guard between the header and the ctypes mirror at run time."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "og_decoder.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct OgLimbsDesc \{(.*?)\} OgLimbsDesc;", text, flags=re.S).group(1)
+    names = [re.search(r"(\w+)\s*$", part).group(1) for decl in body.split(";") if decl.strip() for part in decl.split(",")]
+    assert names == [n for n, _ in _lib.LimbsDesc._fields_] and len(names) == 28
+    lib = _lib.load()
+    d = _lib.LimbsDesc()
+    assert d.size == ctypes.sizeof(_lib.LimbsDesc)
+    d.size -= 8
+    rc = lib.og_generate_limbs_f32(d, ctypes.c_void_p(16), 1 << 20, None)
+    assert rc == _lib.OG_EINVAL and b"descriptor size" in lib.og_last_error()
+    rc = lib.og_collect_limbs_f32(ctypes.c_void_p(16), ctypes.c_void_p(16), d, None)
+    assert rc == _lib.OG_EINVAL and b"descriptor size" in lib.og_last_error()
+    err = pytest.raises(_lib.OgError, _lib.check, rc, lib).value
+    assert err.code == _lib.OG_EINVAL and "(code -1)" in str(err)
+
+
 def test_library_exports_every_declared_symbol():
     og_build.build()
     lib = ctypes.CDLL(_lib.LIB_PATH)

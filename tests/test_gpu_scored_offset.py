@@ -302,4 +302,4 @@ def test_scored_entry_points_validate(dev):
         proc.limb_collect.generate_limbs_fused(hm, off, scored_ks=4)
     with pytest.raises(NotImplementedError):
         proc.limb_collect.generate_limbs_fused(hm, off, vector_nd=4, scored_ks=3)
-    assert lib.og_abi_version() == 3
+    assert lib.og_abi_version() == 4

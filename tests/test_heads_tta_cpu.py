@@ -150,19 +150,87 @@ def test_new_entry_points_validate_their_arguments():
     rc = lib.og_scale_accumulate_heads_f32(one, one, None, one, 1, 0, 17, 19, 8, 8, None, None, None, one, 8, 8, 3, 1.0, one, one, None, one,
                                            None)
     assert rc == _lib.OG_EINVAL and b"mode" in lib.og_last_error()
-    args = (1, 17, 16, 16, one, one, 19, 8, 0.1, 0.5, 1.0, None, None, one, one, 1 << 20, None)
-    rc = lib.og_generate_limbs_fused_flip_heads_f32(one, one, one, one, one, 0, None, 0, None, 0, *args)
-    assert rc == _lib.OG_EINVAL and b"neither head" in lib.og_last_error()
-    rc = lib.og_generate_limbs_fused_flip_heads_f32(one, one, one, one, one, 2, one, 2, None, 0, *args)
-    assert rc == _lib.OG_EINVAL and b"ksize" in lib.og_last_error()
-    rc = lib.og_generate_limbs_fused_flip_heads_f32(one, one, one, one, one, 0, one, 1, None, 0, *args)
-    assert rc == _lib.OG_EINVAL and b"scales_mode" in lib.og_last_error()
-    rc = lib.og_generate_limbs_fused_flip_heads_f32(one, None, one, one, one, 0, one, 2, None, 0, *args)
-    assert rc == _lib.OG_EINVAL and b"null pointer" in lib.og_last_error()
+
+
+def limbs_refusal(collect=False, **fields):
+    """og_generate_limbs_f32 (or og_collect_limbs_f32) on the folded K1-fused flip form at 64 x 64 with `fields` changed -> (code, message)"""
+    lib, one = _lib.load(), ctypes.c_void_p(16)      # never dereferenced
+    form = dict(hmps=one, hm_lowres=1, kp_perm=one, offs=one, off_lowres=1, vector_nd=2, limb_perm=one, reserve_mask=one, N=1, C=17, H=64,
+                W=64, jf=one, jt=one, L=19, k=8, thre_hmp=0.1, min_len=0.5, resize_factor=1.0, limbs=one)
+    d = _lib.LimbsDesc(**dict(form, **fields))
+    rc = lib.og_collect_limbs_f32(one, one, d, None) if collect else lib.og_generate_limbs_f32(d, one, 1 << 20, None)
+    return rc, lib.og_last_error()
+
+
+def test_flip_heads_form_validates_its_arguments():
+    """What og_generate_limbs_fused_flip_heads_f32 refused, through the descriptor (its `neither head` refusal went with it: that
+    combination is the flip form)."""
+    rc, msg = limbs_refusal(score_ksize=2, scales=ctypes.c_void_p(16), scales_mode=2)
+    assert rc == _lib.OG_EINVAL and b"ksize" in msg
+    rc, msg = limbs_refusal(scales=ctypes.c_void_p(16), scales_mode=1)
+    assert rc == _lib.OG_EINVAL and b"scales_mode" in msg
+    rc, msg = limbs_refusal(kp_perm=None, scales=ctypes.c_void_p(16), scales_mode=2)
+    assert rc == _lib.OG_EINVAL and b"null pointer" in msg
     # the jitter head keeps the square-input restriction of decoder/collect.py:158
-    wide = (1, 17, 16, 24) + args[4:]
-    rc = lib.og_generate_limbs_fused_flip_heads_f32(one, one, one, one, one, 0, None, 0, one, 3, *wide)
-    assert rc == _lib.OG_EUNSUPPORTED and b"square" in lib.og_last_error()
+    rc, msg = limbs_refusal(W=96, jitter=ctypes.c_void_p(16), jitter_mode=3)
+    assert rc == _lib.OG_EUNSUPPORTED and b"square" in msg
+
+
+NOFLIP = dict(kp_perm=None, limb_perm=None, reserve_mask=None)
+ONE = ctypes.c_void_p(16)
+
+
+@pytest.mark.parametrize("fields,code,text", [
+    (dict(hm_lowres=0), _lib.OG_EUNSUPPORTED, b"kp_perm folds the stride-4 heat maps"),                  # kp_perm without hm_lowres
+    (dict(limb_perm=None), _lib.OG_EINVAL, b"null pointer"),                                             # kp_perm without limb_perm
+    (dict(reserve_mask=None), _lib.OG_EINVAL, b"null pointer"),                                          # limb_perm without reserve_mask
+    (dict(limb_perm=None, kp_perm=None), _lib.OG_EINVAL, b"null pointer"),                               # reserve_mask without limb_perm
+    (dict(vector_nd=4), _lib.OG_EUNSUPPORTED, b"flip fold needs the stride-4 offsets and 2 components"),
+    (dict(off_lowres=0), _lib.OG_EUNSUPPORTED, b"flip fold needs the stride-4 offsets and 2 components"),
+    (dict(NOFLIP, hm_lowres=0, score_ksize=3), _lib.OG_EUNSUPPORTED, b"scored offsets need the stride-4 maps"),   # hi-res heat maps
+    (dict(NOFLIP, off_lowres=0, score_ksize=3), _lib.OG_EUNSUPPORTED, b"scored offsets need the stride-4 maps"),
+    (dict(NOFLIP, vector_nd=4, score_ksize=3), _lib.OG_EUNSUPPORTED, b"2-component offsets"),
+    (dict(score_ksize=4), _lib.OG_EINVAL, b"ksize"),
+    (dict(score_ksize=9), _lib.OG_EINVAL, b"ksize"),
+    (dict(score_ksize=-1), _lib.OG_EINVAL, b"ksize"),
+    (dict(hm_lowres=0, kp_perm=None, scales=ONE, scales_mode=2), _lib.OG_EUNSUPPORTED, b"only with hm_lowres"),   # flip + scale map, hi-res
+    (dict(hm_lowres=0, kp_perm=None, jitter=ONE, jitter_mode=3), _lib.OG_EUNSUPPORTED, b"only with hm_lowres"),
+    (dict(NOFLIP, scales=ONE, scales_mode=1), _lib.OG_EINVAL, b"scales_mode"),                            # hm_lowres with hi-res scale maps
+    (dict(NOFLIP, jitter=ONE, jitter_mode=1), _lib.OG_EINVAL, b"jitter_mode"),
+    (dict(NOFLIP, scales=ONE), _lib.OG_EINVAL, b"scales_mode"),                                           # a map without its mode
+    (dict(NOFLIP, scales_mode=4, scales=ONE), _lib.OG_EINVAL, b"scales_mode"),
+    (dict(NOFLIP, jitter=ONE, jitter_mode=2), _lib.OG_EINVAL, b"jitter_mode"),
+    (dict(NOFLIP, H=48, jitter=ONE, jitter_mode=3), _lib.OG_EUNSUPPORTED, b"square"),
+    (dict(NOFLIP, vector_nd=4, jitter=ONE, jitter_mode=3), _lib.OG_EUNSUPPORTED, b"square"),
+    (dict(NOFLIP, vector_nd=3), _lib.OG_EUNSUPPORTED, b"vector_nd"),
+    (dict(H=62), _lib.OG_EINVAL, b"multiples of 4"),
+    (dict(NOFLIP, hm_lowres=0, W=66), _lib.OG_EINVAL, b"multiples of 4"),                                # stride-4 offsets alone need it too
+    (dict(NOFLIP, H=1 << 16), _lib.OG_EINVAL, b"bad shape"),                                              # H / 4 < 2^14
+    (dict(L=0), _lib.OG_EINVAL, b"bad shape"),
+    (dict(hmps=None), _lib.OG_EINVAL, b"null pointer"),
+    (dict(limbs=None), _lib.OG_EINVAL, b"null pointer"),
+    (dict(topk_scores=ONE), _lib.OG_EINVAL, b"go together"),
+    (dict(H=8, W=8, k=40), _lib.OG_EINVAL, b"plane border"),
+])
+def test_limbs_descriptor_support_matrix(fields, code, text):
+    """One refusal per rule of validate_limbs_desc (csrc/nms_topk.hip), each from the accepted folded flip form with one thing changed."""
+    rc, msg = limbs_refusal(**fields)
+    assert rc == code and text in msg and b"og_generate_limbs_f32:" in msg, (rc, msg)
+
+
+def test_limbs_descriptor_collect_entry():
+    """og_collect_limbs_f32 on the same descriptor: no flip fold, heat maps only for scored_off, no top-k stage to size k against."""
+    rc, msg = limbs_refusal(collect=True)
+    assert rc == _lib.OG_EUNSUPPORTED and b"og_collect_limbs_f32: the flip fold belongs to og_generate_limbs_f32" in msg
+    rc, msg = limbs_refusal(collect=True, **dict(NOFLIP, hmps=None, score_ksize=3))
+    assert rc == _lib.OG_EINVAL and b"null pointer" in msg
+    rc, msg = limbs_refusal(collect=True, **dict(NOFLIP, vector_nd=3))
+    assert rc == _lib.OG_EUNSUPPORTED and b"vector_nd" in msg
+    rc, msg = limbs_refusal(collect=True, **dict(NOFLIP, hmps=None, k=4096))       # past every rule of the descriptor: the launch's own limit
+    assert rc == _lib.OG_EUNSUPPORTED and b"too large" in msg
+    lib = _lib.load()
+    rc = lib.og_collect_limbs_f32(None, ONE, _lib.LimbsDesc(), None)
+    assert rc == _lib.OG_EINVAL and b"null pointer" in lib.og_last_error()
 
 
 # ---------------------------------------------------------------------------------- merge_scales: checks in front of the device

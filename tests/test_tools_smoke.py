@@ -1,5 +1,5 @@
 """The kept measurement / fixture tools (tools/*.py, tools/experiments/*.py) still fit the library: every one imports, and every
-`lib.og_*` entry point a tool calls is either part of the C ABI (include/og_decoder.h via _lib.SIGNATURES, ABI v3) or one of the
+`lib.og_*` entry point a tool calls is either part of the C ABI (include/og_decoder.h via _lib.SIGNATURES, ABI v4) or one of the
 diagnostic-build symbols (-DOG_*_STAMPS libraries built by tools/build_variants.sh / tools/build_stamps_lib.sh)."""
 import glob
 import os
@@ -25,7 +25,7 @@ def test_every_tool_imports():
 
 def test_tools_call_only_entry_points_of_the_abi():
     from offsetguided_amd import _lib
-    assert _lib.ABI_VERSION == 3
+    assert _lib.ABI_VERSION == 4
     unknown = {}
     for t in TOOLS:
         src = open(t).read()

@@ -10,11 +10,13 @@ checkout's libog_decoder.so and the PARENT commit's, built beside it (--parent-l
 Every figure is the median of TIMED (40) launches after WARM (40), each launch between its own pair of HIP timing events; per arm the
 median over the rounds is reported with the min..max of the rounds (the spread of repeating the same command on the same code).
   (i)   a flip-test request with both heads up to the limbs: the parent's route (K0 og_flip_merge_f32 + the torch-op head merges +
-        K1-fused, restated here on the parent's library) against this commit's folded route (og_generate_limbs_fused_flip_heads_f32);
+        K1-fused, restated here on the parent's library) against this commit's folded route (the scale / jitter pairs in the descriptor);
   (ii)  the same with the fold off: K0 + og_flip_merge_heads_f32 + K1-fused;
   (iii) the scale-merge launch of one scale (flip pair, 96 x 96 -> 160 x 160): four maps against the two-map launch;
   (iv)  K1-fused without heads, plain and folded flip, on both libraries.
 The parent's library lacks the new entry points: its arm types what the library has and runs only what the parent could run.
+Both arms call through this checkout's decoder.collect, i.e. with the descriptor of ABI 4: a parent library built before ABI 4 can no
+longer be loaded for the A/B (profiles/heads_tta_bench.json was recorded against an ABI 3 parent, before the descriptor).
 
     python tools/heads_tta_bench.py [--out profiles/heads_tta_bench.json]
 """

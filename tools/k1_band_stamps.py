@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time points inside the two launches of K1 (library built with -DOG_K1_STAMPS, tools/build_variants.sh): per-workgroup
 wall-clock stamps of band_topk_kernel (entry, set-up done, stream done, wave list compacted, band list stored) and of
-merge_collect_kernel (entry, planes merged, limb rows written), relative to the first band workgroup's entry."""
+merge_collect_kernel (entry, planes merged, limb rows written), relative to the first band workgroup's entry.  The library is typed
+from _lib.SIGNATURES (tools/k1_bench.py: load), i.e. with the descriptor call of ABI 4: one built before ABI 4 cannot be loaded."""
 import ctypes as C
 import os
 import sys
@@ -82,9 +83,9 @@ def main():
     if len(sys.argv) > 2:
         buf0 = np.zeros(2048 * 8, np.int64)
     for it in range(10):
-        _lib.check(lib.og_generate_limbs_f32(_lib.ptr(hrs[it % 3]), _lib.ptr(t_off), 1, 2, None, 0, None, 0, n, c, h, w,
-                                             _lib.ptr(jf), _lib.ptr(jt), L, k, 0.04, 0.5, 1.0, _lib.ptr(sc), _lib.ptr(ix),
-                                             _lib.ptr(limbs), 0, _lib.ptr(ws), ws.numel(), sp), lib)
+        d = _lib.LimbsDesc(hmps=hrs[it % 3], offs=t_off, off_lowres=1, vector_nd=2, N=n, C=c, H=h, W=w, jf=jf, jt=jt, L=L, k=k, thre_hmp=0.04,
+                           min_len=0.5, resize_factor=1.0, topk_scores=sc, topk_inds=ix, limbs=limbs)
+        _lib.check(lib.og_generate_limbs_f32(d, _lib.ptr(ws), ws.numel(), sp), lib)
         torch.cuda.synchronize()
         buf = np.zeros(2048 * 8, np.int64)
         lib.og_k1_band_stamps(buf.ctypes.data)

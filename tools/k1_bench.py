@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""K1 at the generate_limbs boundary (og_generate_limbs_f32 vs og_nms_topk_f32 + og_collect_limbs_full_f32) on the bs8
+"""K1 at the generate_limbs boundary (og_generate_limbs_f32 vs og_nms_topk_f32 + og_collect_limbs_f32) on the bs8
 640x640 synthetic batch: HIP events on the launch stream, several library builds in ONE process (same box, same clocks).
 
   python tools/k1_bench.py [--libs a.so b.so ...] [--iters 40]
 
 For every library: (1) results of og_generate_limbs_f32 == the separate entry points (bitwise), (2) HBM-cold timing (3 rotating
 hi-res batches, 669 MB > Infinity Cache), (3) timing directly behind K1a (the hi-res batch has just been written: the
-decode pipeline's situation), (4) the three-launch form in both situations."""
+decode pipeline's situation), (4) the three-launch form in both situations.
+
+--libs are typed from _lib.SIGNATURES, i.e. with the descriptor call of ABI 4: a library built before ABI 4 cannot be loaded for A/B."""
 import argparse
 import ctypes as C
 import os
@@ -107,16 +109,19 @@ def main():
         sc2 = torch.empty((n, c, k), device=dev)
         ix2 = torch.empty((n, c, k), dtype=torch.int64, device=dev)
 
+        common = dict(offs=t_off, off_lowres=1, vector_nd=2, N=n, C=c, H=h, W=w, jf=jf, jt=jt, L=L, k=k, thre_hmp=0.04, min_len=0.5,
+                      resize_factor=1.0)
+        d_two = [_lib.LimbsDesc(hmps=x, topk_scores=sc2, topk_inds=ix2, limbs=limbs2, **common) for x in hrs]
+        d_fused = [_lib.LimbsDesc(hmps=x, hm_lowres=1, topk_scores=sc2, topk_inds=ix2, limbs=limbs2, **common) for x in lrs]
+        d_three = _lib.LimbsDesc(limbs=limbs3, **common)
+
         def two(i):   # the default form: band kernel + merge-and-pair kernel
-            _lib.check(lib.og_generate_limbs_f32(_lib.ptr(hrs[i % a.rotate]), _lib.ptr(t_off), 1, 2, None, 0, None, 0, n, c, h, w,
-                                                 _lib.ptr(jf), _lib.ptr(jt), L, k, 0.04, 0.5, 1.0, _lib.ptr(sc2), _lib.ptr(ix2),
-                                                 _lib.ptr(limbs2), 0, _lib.ptr(ws1), ws1.numel(), sp), lib)
+            _lib.check(lib.og_generate_limbs_f32(d_two[i % a.rotate], _lib.ptr(ws1), ws1.numel(), sp), lib)
 
         def three(i):
             _lib.check(lib.og_nms_topk_f32(_lib.ptr(hrs[i % a.rotate]), n * c, h, w, k, _lib.ptr(sc), _lib.ptr(ix), _lib.ptr(ws3),
                                            ws3.numel(), sp), lib)
-            _lib.check(lib.og_collect_limbs_full_f32(_lib.ptr(sc), _lib.ptr(ix), _lib.ptr(t_off), 1, 2, None, 0, None, 0, n, c, h,
-                                                     w, _lib.ptr(jf), _lib.ptr(jt), L, k, 0.04, 0.5, 1.0, _lib.ptr(limbs3), sp), lib)
+            _lib.check(lib.og_collect_limbs_f32(_lib.ptr(sc), _lib.ptr(ix), d_three, sp), lib)
 
         ok = True
         for i in range(a.rotate if set(a.forms) >= {'two', 'three'} else 0):
@@ -146,9 +151,7 @@ def main():
             return float(np.median(t)), float(t.min())
 
         def fused(i):   # the production form: x4 bicubic inside the band kernel, merge + pairing in one launch (no hi-res tensor)
-            _lib.check(lib.og_generate_limbs_fused_f32(_lib.ptr(lrs[i % a.rotate]), _lib.ptr(t_off), 2, None, 0, None, 0, n, c, h // 4, w // 4,
-                                                       _lib.ptr(jf), _lib.ptr(jt), L, k, 0.04, 0.5, 1.0, _lib.ptr(sc2), _lib.ptr(ix2),
-                                                       _lib.ptr(limbs2), _lib.ptr(ws1), ws1.numel(), sp), lib)
+            _lib.check(lib.og_generate_limbs_f32(d_fused[i % a.rotate], _lib.ptr(ws1), ws1.numel(), sp), lib)
 
         fns = {'two': two, 'three': three, 'fused': fused}
         res = {f'{f} cold': timed(fns[f]) for f in a.forms}

@@ -7,7 +7,8 @@
 
 Corrections of MI355X_MICROARCH.md (HBM section): counter values are KiB; on gfx950 FETCH_SIZE reports exactly half the
 bytes of a wide coalesced streaming read (16 B per lane) -- doubled here; WRITE_SIZE is exact for 16-B-per-lane stores.
-Calibration in this access pattern: bicubic4_kernel writes N*C*H*W*4 bytes, band_topk_kernel reads them once."""
+Calibration in this access pattern: bicubic4_kernel writes N*C*H*W*4 bytes, band_topk_kernel reads them once.
+(tools/k1_bench.py types its libraries from _lib.SIGNATURES: --libs built before ABI 4, the descriptor call, can no longer be profiled.)"""
 import csv
 import json
 import sys
@@ -28,7 +29,7 @@ def main(fetch_csv, write_csv, out):
     wr = per_kernel(write_csv, 'WRITE_SIZE')
     names = sorted(set(rd) | set(wr))
     table = {n: {'read': round(rd.get(n, 0.0)), 'write': round(wr.get(n, 0.0))} for n in names}
-    three = [n for n in names if n.startswith(('band_topk_kernel', 'merge_collect_kernel'))]   # og_generate_limbs_f32, flags 0
+    three = [n for n in names if n.startswith(('band_topk_kernel', 'merge_collect_kernel'))]   # og_generate_limbs_f32
     single = [n for n in names if n.startswith('generate_limbs_kernel')]
     res = {'hbm_bytes_per_launch': round(sum(table[n]['read'] + table[n]['write'] for n in three)),
            'single_launch_hbm_bytes_per_launch': round(sum(table[n]['read'] + table[n]['write'] for n in single)) if single else None,
@@ -36,7 +37,7 @@ def main(fetch_csv, write_csv, out):
            'note': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/k1_bench.py --iters 10 --rotate 3, bs8 '
                    '640x640); FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half the bytes of wide coalesced reads), '
                    'values are KiB; hbm_bytes_per_launch = band_topk_kernel + merge_collect_kernel '
-                   '(og_generate_limbs_f32, flags 0); calibration: bicubic4_kernel write = 222.8 MB expected',
+                   '(og_generate_limbs_f32); calibration: bicubic4_kernel write = 222.8 MB expected',
            'per_kernel': table}
     json.dump(res, open(out, 'w'), indent=1)
     print(json.dumps(res, indent=1))
