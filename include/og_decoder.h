@@ -608,6 +608,36 @@ int og_affine_joints_f32(const float *joints, const int *n_persons, int N, int P
                          const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr, float *out,
                          void *stream);
 
+/* ---- photometric training augmentation (transforms/image.py:31-41, 55-86; transforms/annotations.py:89-111; DeviceAugment with
+ * PhotoParams) ----  The per-image photometric table photo4 (host int[4 n]) holds {mode, dh, ds, dv}: mode bit 0 = ColorTint with
+ * the deltas (dh, ds, dv) added to H in [0, 180) (clamped to [0, 179], not wrapped), S and V in [0, 255]; bit 1 = Gray
+ * ((19595 R + 38470 G + 7471 B + 2^15) >> 16 on all three channels, PIL's `L`); tint first.  Both are integer specifications of this
+ * library's own, written out in csrc/photometric.h and held bit for bit to tests/photometric_common.py; the tint has the shape of
+ * OpenCV's 8-bit HSV conversion, parity with cv2.cvtColor is NOT claimed (absent from the build); Gray is pinned to PIL.
+ * og_warp_affine_photo_batch_u8: og_warp_affine_batch_u8 with that epilogue between the warped value v and the normalisation: out
+ * = normalise(epilogue(v)); out_u8 (may be NULL) still receives v itself.  With every mode 0 the output equals the plain entry's.
+ * OG_EINVAL as the plain entry, and for a mode beyond 3, |dh| > 180, |ds| > 255 or |dv| > 255.
+ * og_jpeg_roundtrip_batch_u8: JpegCompression.  u8 (device, (N,S,S,3)) = the out_u8 of the warp; for each of the n_selected image
+ * indices in `selected` (host int[]) the planes of out (N,3,S,S) fp32 are overwritten with normalise(epilogue(jpeg(v))), the other
+ * images' planes are not touched; photo4 (host int[4 N], indexed by image; NULL: no epilogue).  jpeg = the shape of baseline JPEG at
+ * 4:2:0 in integer arithmetic of this library's own (16-bit fixed-point YCbCr, 2 x 2 chroma mean, 8 x 8 DCT as two integer matrix
+ * products, Annex K tables scaled by `quality` the libjpeg way, box chroma upsampling, partial MCUs padded by replication),
+ * csrc/jpeg_sim.hip; no bit parity with libjpeg, closeness to PIL measured (profiles/photometric_parity.json).
+ * OG_EINVAL (nothing launched): a null pointer; non-positive N or S, S beyond 16384, negative n_selected; quality outside [1, 100];
+ * a selected index outside [0, N); a bad descriptor of a selected image.  n_selected == 0 launches nothing.
+ * og_affine_joints_jitter_f32: og_affine_joints_f32, then AnnotationJitter on the rows of persons in use of the images with gate[n]
+ * != 0 (host int[N]): x' += eps[n] * (((u_x - 0.5) + shift[n]) * 2), y' likewise, every operation one fp32 operation in this order;
+ * noise (device, (N,P,K,2) fp32, 8-byte aligned) holds u of OUTPUT row (n, p, k); eps, shift host float[N].  v is not re-tested (the
+ * reference jitters after the warp).  An image with gate 0, and every padding row, equals og_affine_joints_f32. */
+int og_warp_affine_photo_batch_u8(const unsigned char *raw, const long *offsets, const int *hw4, int n, const double *D, int S,
+                                  const unsigned char *border3, const float *mean3, const float *std3, float *out,
+                                  unsigned char *out_u8, const int *photo4, void *stream);
+int og_jpeg_roundtrip_batch_u8(const unsigned char *u8, int N, int S, const int *selected, int n_selected, int quality,
+                               const int *photo4, const float *mean3, const float *std3, float *out, void *stream);
+int og_affine_joints_jitter_f32(const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
+                                const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr,
+                                const float *noise, const int *gate, const float *eps, const float *shift, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

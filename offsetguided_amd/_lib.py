@@ -105,6 +105,9 @@ SIGNATURES = {
     "og_warp_affine_batch_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_warp_affine_mask_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "og_affine_joints_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp]),
+    "og_warp_affine_photo_batch_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_jpeg_roundtrip_batch_u8": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "og_affine_joints_jitter_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -31,9 +31,21 @@
 // terms once per thread, one 16-byte store per NCHW plane.  The taps are read as bytes through L1 (the 16 taps of neighbouring
 // pixels overlap heavily); the source is not staged in LDS (under rotation and scale 0.5 a tile's footprint is large and irregular).
 // LDS holds the 32 x 4 tap table only, computed by the workgroup's first 32 threads.
+//
+// og_warp_affine_photo_batch_u8 is the same kernel with the photometric epilogue of csrc/photometric.h (ColorTint, Gray; a descriptor
+// per image, by value like the geometry) between v and the normalisation: v' = epilogue(v) is what gets normalised, out_u8 still
+// receives v itself (the JPEG round trip of csrc/jpeg_sim.hip reads it).  That instantiation also builds the tint's two division
+// tables (2 KiB) in LDS.  With every mode 0 it stores what og_warp_affine_batch_u8 stores.
+//
+// og_affine_joints_jitter_f32 adds AnnotationJitter (transforms/annotations.py:89-111) behind the keypoint transform: rows of persons
+// in use of a gated image get x += eps * (((u - 0.5) + shift) * 2), y likewise, u the row's two fp32 noise values, every operation one
+// fp32 operation in this order; after the visibility test, which is not repeated (the reference jitters after the warp and never culls).
 #include <math.h>
 
+#include <type_traits>
+
 #include "og_common.h"
+#include "photometric.h"
 
 namespace {
 
@@ -50,6 +62,14 @@ struct WarpArgs {
     float mean[3], stdv[3];
     int border[3];
 };
+
+// photometric descriptors of a launch's images; the plain instantiations carry an empty argument instead
+struct PhotoBatch {
+    photo::Desc d[kWarpBatchMax];
+};
+struct NoPhoto {};
+template <bool PHOTO>
+using PhotoArg = std::conditional_t<PHOTO, PhotoBatch, NoPhoto>;
 
 // specification step 2
 __device__ __forceinline__ void phase_taps(int p, short (&t)[4])
@@ -85,13 +105,21 @@ __device__ __forceinline__ int warp_coord(double m0, int x, int row)
 
 // C = channels per source pixel (3: images, 1: mask planes).  NORM: write the normalised fp32 NCHW tensor (and v as NHWC bytes if
 // out_u8 is not null); otherwise v goes to out_u8 (N,S,S) planes.  vec4: S % 4 == 0 and the outputs are 16-byte (fp32) / 4-byte
-// (planes) aligned, so a thread's four values leave in one store.
-template <int C, bool NORM>
+// (planes) aligned, so a thread's four values leave in one store.  PHOTO: csrc/photometric.h between v and the normalisation.
+template <int C, bool NORM, bool PHOTO = false>
 __global__ void __launch_bounds__(256)
 warp_affine_kernel(const unsigned char *__restrict__ raw, WarpBatch b, WarpArgs a, int S, int tiles_x, float *__restrict__ out_f,
-                   unsigned char *__restrict__ out_u8, int vec4)
+                   unsigned char *__restrict__ out_u8, int vec4, PhotoArg<PHOTO> pb)
 {
+    static_assert(!PHOTO || (NORM && C == 3), "the photometric epilogue works on the RGB triple that gets normalised");
     __shared__ short taps[32][4];
+    const int *sdiv = nullptr, *hdiv = nullptr;
+    if constexpr (PHOTO) {
+        __shared__ int divs[2][256];
+        photo::build_tables(divs[0], divs[1], threadIdx.x);
+        sdiv = divs[0];
+        hdiv = divs[1];
+    }
     if (threadIdx.x < 32) {
         short t[4];
         phase_taps(threadIdx.x, t);
@@ -150,6 +178,22 @@ warp_affine_kernel(const unsigned char *__restrict__ raw, WarpBatch b, WarpArgs 
     }
     const size_t px0 = ((size_t)n * S + y) * S + x0;           // pixel index of (n, y, x0) in an (N,S,S) plane
     if (NORM) {
+        auto store_u8 = [&]() {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (x0 + i < S) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) out_u8[(px0 + i) * C + c] = (unsigned char)v[i][c];
+                }
+        };
+        if constexpr (PHOTO) {
+            if (out_u8) store_u8();                            // v itself, before the epilogue
+            const photo::Desc d = pb.d[n];
+            if (d.mode) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) photo::apply(v[i][0], v[i][1], v[i][2], d, sdiv, hdiv);
+            }
+        }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float o[4];
@@ -164,13 +208,8 @@ warp_affine_kernel(const unsigned char *__restrict__ raw, WarpBatch b, WarpArgs 
                     if (x0 + i < S) dst[i] = o[i];
             }
         }
-        if (out_u8) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (x0 + i < S) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) out_u8[(px0 + i) * C + c] = (unsigned char)v[i][c];
-                }
+        if constexpr (!PHOTO) {
+            if (out_u8) store_u8();
         }
     } else {
         if (vec4) {
@@ -193,11 +232,15 @@ struct JointBatch {
 struct LrTable {
     int left[kLrMax], right[kLrMax], n;
 };
+struct JitterBatch {
+    float eps[kWarpBatchMax], shift[kWarpBatchMax];
+    int gate[kWarpBatchMax];
+};
 
-// one thread per keypoint row (n, p, k) of joints (N,P,K,4): rows [x, y, v, scale]
+// one thread per keypoint row (n, p, k) of joints (N,P,K,4): rows [x, y, v, scale]; noise (N,P,K) pairs or null (no jitter at all)
 __global__ void __launch_bounds__(256)
 affine_joints_kernel(const float4 *__restrict__ joints, const int *__restrict__ n_persons, JointBatch b, LrTable lr, int P, int K,
-                     float S_w, float S_h, float4 *__restrict__ out)
+                     float S_w, float S_h, float4 *__restrict__ out, const float2 *__restrict__ noise, JitterBatch jb)
 {
     const int n = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P * K) return;
@@ -223,6 +266,11 @@ affine_joints_kernel(const float4 *__restrict__ joints, const int *__restrict__ 
     o.y = (float)__dadd_rn(__dadd_rn(__dmul_rn(M[3], x), __dmul_rn(M[4], y)), M[5]);
     o.w = (float)__dmul_rn((double)j.w, b.scale[n]);
     o.z = (o.x <= 0.f || o.y <= 0.f || o.x > S_w || o.y > S_h) ? 0.f : j.z;   // (a NaN coordinate keeps v, as the reference's comparison does)
+    if (noise && jb.gate[n]) {                                 // AnnotationJitter: after the visibility test, the noise of the OUTPUT row
+        const float2 u = noise[base + idx];
+        o.x = o.x + jb.eps[n] * (((u.x - 0.5f) + jb.shift[n]) * 2.f);
+        o.y = o.y + jb.eps[n] * (((u.y - 0.5f) + jb.shift[n]) * 2.f);
+    }
     out[base + idx] = o;
 }
 
@@ -238,15 +286,19 @@ bool warp_rows_in_range(const double *D, int n, int S)
     return true;
 }
 
-template <int C, bool NORM>
+template <int C, bool NORM, bool PHOTO = false>
 int warp_launch(const char *name, const unsigned char *raw, const long *offsets, const int *hw4, int n, const double *D, int S,
-                const WarpArgs &a, float *out_f, unsigned char *out_u8, hipStream_t stream)
+                const WarpArgs &a, float *out_f, unsigned char *out_u8, hipStream_t stream, const int *photo4 = nullptr)
 {
     OG_REQUIRE(n > 0 && S > 0 && S <= 16384, OG_EINVAL, "%s: bad shape", name);
     for (int i = 0; i < n; ++i)
         OG_REQUIRE(hw4[i * 4] > 0 && hw4[i * 4 + 1] > 0 && (long)hw4[i * 4] * hw4[i * 4 + 1] < (1l << 28) && offsets[i] >= 0, OG_EINVAL,
                    "%s: image %d: bad shape", name, i);
     OG_REQUIRE(warp_rows_in_range(D, n, S), OG_EINVAL, "%s: a source coordinate could reach 2^20 (or D is not finite)", name);
+    if constexpr (PHOTO) {
+        for (int i = 0; i < n; ++i)
+            OG_REQUIRE(photo::desc_ok(photo4 + i * 4), OG_EINVAL, "%s: image %d: bad photometric descriptor", name, i);
+    }
     const int tiles_x = (S + kWarpTW - 1) / kWarpTW, tiles_y = (S + kWarpTH - 1) / kWarpTH;
     const size_t align = NORM ? 15 : 3;
     const int vec4 = S % 4 == 0 && ((size_t)(NORM ? (const void *)out_f : (const void *)out_u8) & align) == 0;
@@ -258,9 +310,17 @@ int warp_launch(const char *name, const unsigned char *raw, const long *offsets,
             b.off[i] = offsets[j]; b.h[i] = hw4[j * 4]; b.w[i] = hw4[j * 4 + 1];
             for (int k = 0; k < 6; ++k) b.D[i][k] = D[j * 6 + k];
         }
+        PhotoArg<PHOTO> pb;
+        if constexpr (PHOTO) {
+            for (int i = 0; i < kWarpBatchMax; ++i) {
+                const int *p4 = photo4 + (first + (i < m ? i : 0)) * 4;
+                pb.d[i] = photo::Desc{p4[0], p4[1], p4[2], p4[3]};
+            }
+        }
         const size_t plane = (size_t)first * S * S;
-        hipLaunchKernelGGL((warp_affine_kernel<C, NORM>), dim3((unsigned)(tiles_x * tiles_y), (unsigned)m), dim3(256), 0, stream, raw, b,
-                           a, S, tiles_x, out_f ? out_f + plane * C : nullptr, out_u8 ? out_u8 + plane * (NORM ? C : 1) : nullptr, vec4);
+        hipLaunchKernelGGL((warp_affine_kernel<C, NORM, PHOTO>), dim3((unsigned)(tiles_x * tiles_y), (unsigned)m), dim3(256), 0, stream,
+                           raw, b, a, S, tiles_x, out_f ? out_f + plane * C : nullptr, out_u8 ? out_u8 + plane * (NORM ? C : 1) : nullptr,
+                           vec4, pb);
         OG_LAUNCH_CHECK(name);
     }
     return OG_OK;
@@ -279,6 +339,17 @@ OG_API int og_warp_affine_batch_u8(const unsigned char *raw, const long *offsets
     return warp_launch<3, true>(name, raw, offsets, hw4, n, D, S, a, out, out_u8, (hipStream_t)stream);
 }
 
+OG_API int og_warp_affine_photo_batch_u8(const unsigned char *raw, const long *offsets, const int *hw4, int n, const double *D, int S,
+                                         const unsigned char *border3, const float *mean3, const float *std3, float *out,
+                                         unsigned char *out_u8, const int *photo4, void *stream)
+{
+    const char *name = "og_warp_affine_photo_batch_u8";
+    OG_REQUIRE(raw && offsets && hw4 && D && border3 && mean3 && std3 && out && photo4, OG_EINVAL, "%s: null pointer", name);
+    WarpArgs a;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; a.border[c] = border3[c]; }
+    return warp_launch<3, true, true>(name, raw, offsets, hw4, n, D, S, a, out, out_u8, (hipStream_t)stream, photo4);
+}
+
 OG_API int og_warp_affine_mask_u8(const unsigned char *masks, const long *offsets, const int *hw4, int n, const double *D, int S,
                                   int border, unsigned char *out, void *stream)
 {
@@ -290,11 +361,13 @@ OG_API int og_warp_affine_mask_u8(const unsigned char *masks, const long *offset
     return warp_launch<1, false>(name, masks, offsets, hw4, n, D, S, a, nullptr, out, (hipStream_t)stream);
 }
 
-OG_API int og_affine_joints_f32(const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
-                                const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr, float *out,
-                                void *stream)
+namespace {
+
+// both keypoint entry points: noise == null is the plain transform
+int joints_launch(const char *name, const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
+                  const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr, const float *noise,
+                  const int *gate, const float *eps, const float *shift, float *out, void *stream)
 {
-    const char *name = "og_affine_joints_f32";
     OG_REQUIRE(joints && M && flip && scale && out && (n_lr == 0 || (left && right)), OG_EINVAL, "%s: null pointer", name);
     OG_REQUIRE(N > 0 && P > 0 && K > 0 && (long)P * K < (1l << 24), OG_EINVAL, "%s: bad shape", name);
     OG_REQUIRE(n_lr >= 0 && n_lr <= kLrMax, OG_EINVAL, "%s: at most %d left / right pairs", name, kLrMax);
@@ -308,16 +381,38 @@ OG_API int og_affine_joints_f32(const float *joints, const int *n_persons, int N
     for (int first = 0; first < N; first += kWarpBatchMax) {
         const int m = N - first < kWarpBatchMax ? N - first : kWarpBatchMax;
         JointBatch b;
+        JitterBatch jb = {};
         for (int i = 0; i < kWarpBatchMax; ++i) {
             const int j = first + (i < m ? i : 0);
             for (int k = 0; k < 6; ++k) b.M[i][k] = M[j * 6 + k];
             b.scale[i] = scale[j]; b.flip[i] = flip[j];
+            if (noise) { jb.gate[i] = gate[j]; jb.eps[i] = eps[j]; jb.shift[i] = shift[j]; }
         }
         const size_t rows = (size_t)first * P * K;
         hipLaunchKernelGGL(affine_joints_kernel, dim3((unsigned)((P * K + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
                            reinterpret_cast<const float4 *>(joints) + rows, n_persons ? n_persons + first : nullptr, b, lr, P, K, S_w, S_h,
-                           reinterpret_cast<float4 *>(out) + rows);
+                           reinterpret_cast<float4 *>(out) + rows, noise ? reinterpret_cast<const float2 *>(noise) + rows : nullptr, jb);
         OG_LAUNCH_CHECK(name);
     }
     return OG_OK;
+}
+
+}  // namespace
+
+OG_API int og_affine_joints_f32(const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
+                                const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr, float *out,
+                                void *stream)
+{
+    return joints_launch("og_affine_joints_f32", joints, n_persons, N, P, K, M, flip, scale, S_w, S_h, left, right, n_lr, nullptr, nullptr,
+                         nullptr, nullptr, out, stream);
+}
+
+OG_API int og_affine_joints_jitter_f32(const float *joints, const int *n_persons, int N, int P, int K, const double *M, const int *flip,
+                                       const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr,
+                                       const float *noise, const int *gate, const float *eps, const float *shift, float *out, void *stream)
+{
+    const char *name = "og_affine_joints_jitter_f32";
+    OG_REQUIRE(noise && gate && eps && shift, OG_EINVAL, "%s: null pointer", name);
+    OG_REQUIRE(((size_t)noise & 7) == 0, OG_EINVAL, "%s: noise not 8-byte aligned", name);
+    return joints_launch(name, joints, n_persons, N, P, K, M, flip, scale, S_w, S_h, left, right, n_lr, noise, gate, eps, shift, out, stream);
 }

@@ -57,6 +57,15 @@ def train_cli(argv=None):
     g.add_argument('--min-stretch', default=0.95, type=float, help='lower bound of the relative image length stretch')
     g.add_argument('--max-stretch', default=1.05, type=float, help='upper bound of the relative image length stretch')
     g.add_argument('--max-translate', default=150, type=int, help='upper bound of shifting the image during augmentation')
+    g = p.add_argument_group('photometric augmentation behind the warp, with --augment (data/factory.py:250-265; all off by default)')
+    g.add_argument('--color-tint-prob', default=0., type=float,
+                   help='probability of ColorTint (hue +-10, saturation +-40, value +-30 in 8-bit HSV); the reference trains with 0.2')
+    g.add_argument('--gray-prob', default=0., type=float, help='probability of Gray (the reference never composes it)')
+    g.add_argument('--jpeg-prob', default=0., type=float,
+                   help='probability of a JpegCompression round trip; 0.1 in the reference, where the step is commented out')
+    g.add_argument('--jpeg-quality', default=50, type=int, help='quality of that round trip, 1...100 (the reference: 50)')
+    g.add_argument('--annotation-jitter-prob', default=0., type=float,
+                   help='probability of AnnotationJitter (+-0.5 px on every keypoint); 0.1 in the reference, where the step is commented out')
     g = p.add_argument_group('optimizer configuration')
     g.add_argument('--optimizer', type=str, default='adam', choices=['sgd', 'adam'])
     g.add_argument('--learning-rate', type=float, default=2.5e-4, help='learning rate for world size 1')
@@ -224,6 +233,8 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
         torch.cuda.synchronize(dev)               # the events are complete before they are read
         us =[a.elapsed_time(b) * 1e3 for a, b in augment_events]
         extra['augment_us'] = round(sum(us) / len(us), 1)
+        extra['photo_probs'] = {'color_tint': args.color_tint_prob, 'gray': args.gray_prob, 'jpeg': args.jpeg_prob,
+                                'jpeg_quality': args.jpeg_quality, 'annotation_jitter': args.annotation_jitter_prob}
     nosync_s = timed(max(args.bench_steps // 2, 1), 0, sync_grads=False) if world > 1 else step_s
     n_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
     payload_dtype = torch.bfloat16 if (args.grad_compress == 'bf16' and use_cuda) else torch.float32
@@ -315,7 +326,10 @@ def main(argv=None):
         encoders = encoder.factory_heads(['hmp', 'omp'], args.square_length, [4, 4], dev)
     if args.augment:
         # raw uint8 images on 640 x 480 canvases and their un-augmented annotations; every step draws a new crop of its entry
-        augment = transforms.DeviceAugment(args.square_length, args, device=dev)
+        photo = transforms.PhotoParams(tint_prob=args.color_tint_prob, gray_prob=args.gray_prob, jpeg_prob=args.jpeg_prob,
+                                       jpeg_quality=args.jpeg_quality, jitter_prob=args.annotation_jitter_prob)
+        augment = transforms.DeviceAugment(args.square_length, args, device=dev, photo_params=photo,
+                                           np_rng=np.random.RandomState(1000 * rank + 11))
         for i in range(4):
             joints, n_persons = synthetic_annotations(1000 * rank + i, args.batch_size, 480, 640)
             pool.append((synthetic_raw_images(1000 * rank + i, joints, n_persons, 480, 640), joints, n_persons,

@@ -18,6 +18,7 @@ from .. import _lib
 from ..config import data_mean, data_std
 from ..config.coco_data import LEFT_INDEX, RIGHT_INDEX
 from .pad import FILL
+from .photometric import draw_photo, photo_table
 
 COORD_LIMIT = float(1 << 20)   # the device kernel computes source coordinates in int32 with 10 + 5 fractional bits
 
@@ -126,9 +127,17 @@ class DeviceAugment:
     n_persons (N,) int32, mask_miss a list of (h, w) uint8 arrays of the images' sizes -> (images (N,3,S,S) fp32 normalised, joints
     (N,P,17,4), mask (N,S,S) uint8 or None, all on the device; mats (N,3,3) float64 numpy).  Images, masks and annotations are packed
     into one pinned staging buffer and copied once; everything is queued on the current stream and the call never waits for the
-    device (a staging buffer whose last copy is still in flight is left alone and a new one is taken)."""
+    device (a staging buffer whose last copy is still in flight is left alone and a new one is taken).
+    photo_params (transforms.PhotoParams): the reference's RandomApply steps behind the warp -- AnnotationJitter, JpegCompression,
+    ColorTint, Gray --, drawn per image after the matrices in the order transforms/photometric.py documents (gates from `rng`, the
+    tint's deltas from `np_rng`, default numpy.random, the jitter's noise from torch's CPU generator) and kept in `last_photo`.  With
+    every probability 0 (the default) nothing is drawn and the launches are the ones above.  Otherwise the image launch is
+    og_warp_affine_photo_batch_u8 (tint and gray between the warp and the normalisation, still ONE launch), images with a JPEG
+    round trip are redone from the warped bytes by og_jpeg_roundtrip_batch_u8, and the keypoints go through
+    og_affine_joints_jitter_f32, the noise riding in the same staging buffer."""
 
-    def __init__(self, dst_size, aug_params, crop_roi=True, device='cuda:0', mean=data_mean, std=data_std, border=FILL, mask_border=255):
+    def __init__(self, dst_size, aug_params, crop_roi=True, device='cuda:0', mean=data_mean, std=data_std, border=FILL, mask_border=255,
+                 photo_params=None, np_rng=None):
         assert isinstance(dst_size, int), 'the device warp writes a square crop'
         self.transform = WarpAffineTransforms(dst_size, aug_params=aug_params, crop_roi=crop_roi)
         self.size, self.device = dst_size, torch.device(device)
@@ -139,6 +148,7 @@ class DeviceAugment:
         self._left, self._right = (C.c_int * n_lr)(*LEFT_INDEX), (C.c_int * n_lr)(*RIGHT_INDEX)
         self._stage, self._turn = [None, None, None], 0
         self.last_params = None
+        self.photo_params, self.np_rng, self.last_photo = photo_params, np_rng, None
 
     def _staging(self, nbytes):
         buf = self._stage[self._turn]
@@ -161,10 +171,14 @@ class DeviceAugment:
         assert joints.ndim == 4 and joints.shape[0] == n and joints.shape[3] == 4 and n_persons.shape == (n,)
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in raw_images]
         self.last_params, mats = self.matrices(joints, n_persons, sizes, rng)
-        return self.apply(raw_images, joints, n_persons, mats, self.last_params, mask_miss)
+        self.last_photo = None
+        if self.photo_params is not None and self.photo_params.steps():
+            self.last_photo = draw_photo(self.photo_params, n_persons, joints.shape[2], rng, self.np_rng)
+        return self.apply(raw_images, joints, n_persons, mats, self.last_params, mask_miss, self.last_photo)
 
-    def apply(self, raw_images, joints, n_persons, mats, params, mask_miss=None):
-        """The device work for given matrices (and the draws they came from: flip and the scales go to the keypoints)."""
+    def apply(self, raw_images, joints, n_persons, mats, params, mask_miss=None, photo=None):
+        """The device work for given matrices (and the draws they came from: flip and the scales go to the keypoints) and, if any,
+        the photometric draws (draw_photo's list of dicts)."""
         lib = _lib.load()
         n, S, dev = len(raw_images), self.size, self.device
         if dev.type != 'cuda':
@@ -178,6 +192,12 @@ class DeviceAugment:
         joints_at = _align16(mask_at + mask_bytes)
         np_at = _align16(joints_at + joints.nbytes)
         total = np_at + n_persons.nbytes
+        table = photo_table(photo) if photo else None
+        jpeg = sorted({d['jpeg'] for d in photo if d['jpeg'] is not None}) if photo else []
+        jittered = [i for i, d in enumerate(photo) if d['jitter'] is not None] if photo else []
+        noise_at, noise_bytes = _align16(total), joints.nbytes // 2
+        if jittered:
+            total = noise_at + noise_bytes
         stage = self._staging(total)
         stage_np = stage[0].numpy()
         offs, hw4, o = (C.c_long * n)(), (C.c_int * (4 * n))(), 0
@@ -197,6 +217,11 @@ class DeviceAugment:
                 o += h * w
         stage_np[joints_at:joints_at + joints.nbytes] = joints.reshape(-1).view(np.uint8)
         stage_np[np_at:np_at + n_persons.nbytes] = n_persons.view(np.uint8)
+        if jittered:
+            noise = stage_np[noise_at:noise_at + noise_bytes].view(np.float32).reshape(joints.shape[:3] + (2,))
+            noise[:] = 0
+            for i in jittered:
+                noise[i, :int(n_persons[i])] = photo[i]['jitter']
         dev_raw = torch.empty(total, dtype=torch.uint8, device=dev)
         dev_raw.copy_(stage[0][:total], non_blocking=True)
         stage[1] = torch.cuda.Event()
@@ -204,8 +229,18 @@ class DeviceAugment:
         stream = _lib.stream_ptr(dev)
         Dc = D.ctypes.data_as(C.c_void_p)
         images = torch.empty((n, 3, S, S), dtype=torch.float32, device=dev)
-        _lib.check(lib.og_warp_affine_batch_u8(_lib.ptr(dev_raw), offs, hw4, n, Dc, S, self._border, self._mean, self._std,
-                                               _lib.ptr(images), None, stream), lib)
+        if table is not None and (table[:, 0].any() or jpeg):
+            warped = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) if jpeg else None
+            tc = table.ctypes.data_as(C.c_void_p)
+            _lib.check(lib.og_warp_affine_photo_batch_u8(_lib.ptr(dev_raw), offs, hw4, n, Dc, S, self._border, self._mean, self._std,
+                                                         _lib.ptr(images), _lib.ptr(warped) if jpeg else None, tc, stream), lib)
+            for quality in jpeg:
+                sel = [i for i, d in enumerate(photo) if d['jpeg'] == quality]
+                _lib.check(lib.og_jpeg_roundtrip_batch_u8(_lib.ptr(warped), n, S, (C.c_int * len(sel))(*sel), len(sel), int(quality), tc,
+                                                          self._mean, self._std, _lib.ptr(images), stream), lib)
+        else:
+            _lib.check(lib.og_warp_affine_batch_u8(_lib.ptr(dev_raw), offs, hw4, n, Dc, S, self._border, self._mean, self._std,
+                                                   _lib.ptr(images), None, stream), lib)
         mask = None
         if mask_miss is not None:
             mask = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
@@ -217,8 +252,14 @@ class DeviceAugment:
         if joints.shape[1] > 0:
             flips = (C.c_int * n)(*[int(bool(p[0])) for p in params])
             scales = (C.c_double * n)(*[math.sqrt((p[3] * p[2]) * (p[4] * p[2])) for p in params])
-            _lib.check(lib.og_affine_joints_f32(_lib.ptr(joints_dev), _lib.ptr(np_dev), n, joints.shape[1], joints.shape[2],
-                                                M.ctypes.data_as(C.c_void_p), flips, scales, float(self.transform.in_size[0]),
-                                                float(self.transform.in_size[1]), self._left, self._right, len(self._left),
-                                                _lib.ptr(out_joints), stream), lib)
+            jargs = (_lib.ptr(joints_dev), _lib.ptr(np_dev), n, joints.shape[1], joints.shape[2], M.ctypes.data_as(C.c_void_p), flips,
+                     scales, float(self.transform.in_size[0]), float(self.transform.in_size[1]), self._left, self._right, len(self._left))
+            if jittered:
+                pp = self.photo_params
+                gate = (C.c_int * n)(*[int(d['jitter'] is not None) for d in photo])
+                eps, shift = (C.c_float * n)(*[float(pp.jitter_epsilon)] * n), (C.c_float * n)(*[float(pp.jitter_shift)] * n)
+                _lib.check(lib.og_affine_joints_jitter_f32(*jargs, _lib.ptr(dev_raw[noise_at:]), gate, eps, shift, _lib.ptr(out_joints),
+                                                           stream), lib)
+            else:
+                _lib.check(lib.og_affine_joints_f32(*jargs, _lib.ptr(out_joints), stream), lib)
         return images, out_joints, mask, np.asarray(mats, np.float64)
