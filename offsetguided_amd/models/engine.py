@@ -150,6 +150,16 @@ def _torch_conv(name, x, weight, stride=1, padding=0):
 
 _warm_streams = {}
 _n_engines = 0
+_side_owner = {}        # handle of a side stream -> the (device, engine) it was made for
+
+
+def _release_side(stream, key):
+    """A dead engine's side stream goes back to _lib's free list ONCE: the shared deep stream sits in the _side table of every deep
+    level of both stacks, and each table evicts on its own -- released from the second table after the first release had already handed
+    the handle to a new engine, it was given out again, and two live engines (two lanes in flight) queued their branches on one stream."""
+    if _side_owner.get(stream.cuda_stream) == key:
+        del _side_owner[stream.cuda_stream]
+        _lib.release_stream(stream)
 
 
 def _conv3x3_workspace(device, nbytes):
@@ -541,7 +551,8 @@ class _Level:
                     # eagerly and still needs its stream; with 32 live engines the table simply grows)
                     dead = next((k for k in self._side if k[1] not in _live_engines), None)
                     if dead is not None:
-                        _lib.release_stream(self._side.pop(dead))
+                        _release_side(self._side.pop(dead), dead)
+                _side_owner.setdefault(side.cuda_stream, key)
                 self._side[key] = side
             box = {}
             trunk_first = bool(TRUNK_FIRST) and self.depth >= TRUNK_FIRST

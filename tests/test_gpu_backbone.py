@@ -575,7 +575,10 @@ def test_engine_other_shapes_match_eager(dev, batch, height, width):
         out = eng(x)
         first = [out[h][0][-1].clone() for h in (0, 1)]           # (the engine re-uses its output buffers: compare copies)
         _check_heads(ref, out, dtype, f'{batch}x{height}x{width}')
-        for _ in range(5):                                        # graph replays: bit-identical results, run after run
+        other = 100 * torch.randn_like(x)
+        for i in range(5):                                        # graph replays: bit-identical results, run after run --
+            if i % 2:                                             # also behind a replay on another input: a consumer ahead of its
+                eng(other)                                        # producer would read that replay's activation, not this one's
             out2 = eng(x)
             for h in (0, 1):
                 assert torch.equal(first[h], out2[h][0][-1]), f'{dtype} {batch}x{height}x{width}: a replay differs from the first run'
@@ -591,7 +594,10 @@ def test_engine_replays_are_bit_identical(dev, shape):
     x = torch.randn(shape[0], 3, shape[1], shape[2], device=dev)
     eng = models.InferenceEngine(model, *shape, device=dev, dtype=torch.float16)
     first = [o.clone() for o in eng.forward_raw(x)]
-    for _ in range(8):
+    other = 100 * torch.randn_like(x)
+    for i in range(8):
+        if i % 2:                        # a replay on another input in between: stale reads would no longer hold the right values
+            eng.forward_raw(other)
         out = eng.forward_raw(x)
         assert all(torch.equal(a, b) for a, b in zip(first, out))
 
