@@ -638,6 +638,40 @@ int og_affine_joints_jitter_f32(const float *joints, const int *n_persons, int N
                                 const double *scale, float S_w, float S_h, const int *left, const int *right, int n_lr,
                                 const float *noise, const int *gate, const float *eps, const float *shift, float *out, void *stream);
 
+/* ---- COCO keypoint scoring (COCOeval with iouType='keypoints', pycocotools/cocoeval.py: computeOks, evaluateImg;
+ * offsetguided_amd.cocoeval.KeypointEval) ----  Packed batches of I images, all arithmetic IEEE double.  Image i owns detections
+ * det_off[i] .. det_off[i + 1] (already sorted by descending score and truncated, at most 64 each), ground truths gt_off[i] ..
+ * gt_off[i + 1] (file order, any count) and the row-major d_i x g_i block of `oks` that starts at pair_off[i] (the running sum of d_i
+ * g_i).  det_off, gt_off (int32[I + 1]) and pair_off (int64[I + 1]) are device pointers; D, G and n_pairs are their last entries.
+ * og_oks_matrix_f64: dets (D,17,3) and gts (G,17,3) rows [x, y, v], gt_area[G], gt_bbox[4 G] rows [x, y, w, h], sigmas (host
+ * double[17]) -> oks[n_pairs].  One thread per pair, the image found by bisection over pair_off.  var[k] = (2 sigmas[k])^2; k1 = the
+ * number of keypoints with vg > 0.  k1 > 0: dx = xd - xg, dy = yd - yg, only the keypoints with vg > 0 enter.  k1 == 0: every
+ * keypoint enters with x0 = bx - bw, x1 = bx + 2 bw, y0 = by - bh, y1 = by + 2 bh, dx = max(0, x0 - xd) + max(0, xd - x1), dy
+ * likewise.  e = (dx dx + dy dy) / var[k] / (area_g + 2^-52) / 2, evaluated left to right, no contraction; OKS = the sum of exp(-e)
+ * in ascending k (the device's double exp) divided by the number of keypoints that enter.  n_pairs == 0 launches nothing.
+ * og_oks_match_i32: the greedy matching of every (image, area range a, threshold t) in one launch -- one wavefront per image, lane
+ * a T + t.  area_ranges (host double[2 A]) rows [lo, hi], thresholds (host double[T]); gt_ignore / gt_crowd uint8[G], det_area[D].
+ * gt_ignore_a[a, g] = gt_ignore[g] || area_g < lo_a || area_g > hi_a.  Per detection in order: best = min(t, 1 - 1e-10), m = none;
+ * the ground truths are visited with gt_ignore_a == 0 first, then the others, each group in file order; one that is matched already at
+ * this (a, t) and is not crowd is skipped; the walk stops at the first ignored one once m is set and not ignored; OKS < best is
+ * skipped; otherwise best = OKS, m = g (an equal OKS replaces).  m set: dt_match = m + 1 (m counted within the image), dt_ignore =
+ * gt_ignore_a[a, m], g is marked; else dt_match = 0 and dt_ignore = det_area < lo_a || det_area > hi_a.  Outputs dt_match int32
+ * (A,T,D), dt_ignore uint8 (A,T,D), gt_ignore_a uint8 (A,G).  The matched set of a lane is a bit mask for g_i <= 64 and a slice of
+ * `workspace` above (og_oks_match_workspace_bytes(G, A, T), host arithmetic; always required); the image's OKS block is staged in LDS
+ * up to 1024 pairs and read from global memory above.  Both kernels: no allocation, no synchronisation, graph-capturable.
+ * OG_EINVAL (nothing launched): a null pointer; I <= 0; negative D, G or n_pairs; A or T outside 1..16 or A T > 64; a non-positive
+ * sigma; and, where an offset table is host-visible (pinned), a table that decreases, does not run from 0 to its total, a pair_off
+ * step that is not d_i g_i, or a d_i > 64 (a device-only table is not read by the host: the kernels then treat an image whose entries
+ * leave the totals as empty).  OG_ENOSPC: workspace_bytes too small. */
+int og_oks_matrix_f64(const double *dets, const double *gts, const double *gt_area, const double *gt_bbox, const int32_t *det_off,
+                      const int32_t *gt_off, const int64_t *pair_off, const double *sigmas, int I, int D, int G, int64_t n_pairs,
+                      double *oks, void *stream);
+size_t og_oks_match_workspace_bytes(int G, int A, int T);
+int og_oks_match_i32(const double *oks, const int32_t *det_off, const int32_t *gt_off, const int64_t *pair_off, const double *gt_area,
+                     const unsigned char *gt_ignore, const unsigned char *gt_crowd, const double *det_area, const double *area_ranges,
+                     int A, const double *thresholds, int T, int I, int D, int G, int64_t n_pairs, int32_t *dt_match,
+                     unsigned char *dt_ignore, unsigned char *gt_ignore_a, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,9 @@ SIGNATURES = {
     "og_warp_affine_photo_batch_u8": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_jpeg_roundtrip_batch_u8": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "og_affine_joints_jitter_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_oks_matrix_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_int64, _vp, _vp]),
+    "og_oks_match_workspace_bytes": (_sz, [_i, _i, _i]),
+    "og_oks_match_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures
@@ -142,7 +145,7 @@ def load():
             raise ImportError(f"{LIB_PATH}: ABI version {lib.og_abi_version()} != {ABI_VERSION}; rebuild with "
                               "`python -m offsetguided_amd.build --force`")
         for name, (res, args) in SIGNATURES.items():
-            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32: the ABI only grew) -- a library built before
+            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32, og_oks_*: the ABI only grew) -- a library built before
             # them says so here instead of with a bare AttributeError
             if not hasattr(lib, name):
                 raise ImportError(f"{LIB_PATH} lacks {name}: stale build; rebuild with `python -m offsetguided_amd.build --force`")

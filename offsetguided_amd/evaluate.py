@@ -5,9 +5,11 @@
   batch i+1's backbone is queued before batch i's poses are collected) -> annotations_inverse ->
   COCO-style result dicts.
 
-COCO data loading and pycocotools are not part of this path: `run_images` takes any iterable of
-(images, annos, metas) batches (the reference's collate format, data/factory.py:23-35) and falls back
-to synthetic batches; `validation` needs pycocotools and raises if it is absent.
+COCO data loading is not part of this path: `run_images` takes any iterable of (images, annos, metas)
+batches (the reference's collate format, data/factory.py:23-35) and falls back to synthetic batches.
+`validation` (and `--score` on the command line) scores the results against args.annotation_file: with
+pycocotools when it imports, otherwise -- or with scorer='native' -- with the package's own COCO keypoint
+scorer (cocoeval.KeypointEval: OKS and matching as HIP kernels, csrc/oks.hip), which needs no pycocotools.
 """
 import argparse
 import json
@@ -52,6 +54,11 @@ def evaluate_cli(argv=None):
     parser.add_argument('--test-scales', default=[1.0], type=float, nargs='+', metavar='S',
                         help='multi-scale test (beyond the reference): input scales relative to --long-edge whose head outputs are '
                              'averaged on the grid of scale 1 (which must be in the list) and decoded once')
+    parser.add_argument('--score', action='store_true', default=False,
+                        help='score the results against the annotation file (validation(): COCO keypoint AP / AR; pycocotools when '
+                             'it imports, the native scorer cocoeval.KeypointEval otherwise)')
+    parser.add_argument('--annotation-file', default=None, type=str,
+                        help="COCO keypoint annotations --score reads (default: the --dataset's own file)")
     parser.add_argument('--loader-workers', default=8, type=int)
     parser.add_argument('--all-images', default=False, action='store_true')
     parser.add_argument('--resume', '-r', action='store_true', default=False, help='load --checkpoint-whole')
@@ -82,9 +89,10 @@ def evaluate_cli(argv=None):
         validate_views(args)
     except ValueError as e:
         parser.error(str(e))
-    args.image_dir, args.annotation_file = {
+    args.image_dir, annotation_file = {
         'val': (IMAGE_DIR_VAL, ANNOTATIONS_VAL), 'test': (IMAGE_DIR_TEST, ANNOTATIONS_TEST),
         'test-dev': (IMAGE_DIR_TEST, ANNOTATIONS_TESTDEV)}[args.dataset]
+    args.annotation_file = args.annotation_file or annotation_file
     if args.dataset in ('test', 'test-dev'):
         args.all_images = True
     return args
@@ -515,8 +523,31 @@ class DeviceFeeder:
         return out
 
 
-def validation(args, data_loader=None):
-    """run_images + COCO keypoint evaluation (evaluate.py:303-328); needs pycocotools."""
+def validation(args, data_loader=None, scorer=None):
+    """run_images + COCO keypoint evaluation (evaluate.py:303-328).  scorer: 'pycocotools' (the reference's COCOeval; ImportError
+    without the package), 'native' (cocoeval.KeypointEval on cocoeval.load_ground_truth(args.annotation_file): needs no pycocotools)
+    or None: pycocotools when it imports, native otherwise.  The results JSON is written either way.  -> the COCOeval, or with the
+    native scorer the KeypointEval (.stats, .precision, .recall)."""
+    if scorer not in (None, 'pycocotools', 'native'):
+        raise ValueError(f"validation: scorer must be 'pycocotools', 'native' or None, got {scorer!r}")
+    if scorer is None:
+        try:
+            import pycocotools.cocoeval  # noqa: F401
+            scorer = 'pycocotools'
+        except ImportError:
+            scorer = 'native'
+    if scorer == 'native':
+        from . import cocoeval
+        if not torch.cuda.is_available():
+            raise _lib.OgError('validation: the native scorer needs a HIP device (offsetguided_amd has no CPU path)')
+        res_file = 'data/link2COCO2017/results/person_keypoints_%s_%s_results.json' % (args.dataset, args.dump_name)
+        os.makedirs(os.path.dirname(res_file), exist_ok=True)
+        ground_truth = cocoeval.load_ground_truth(args.annotation_file)
+        results, ids = run_images(args, data_loader)
+        json.dump(results, open(res_file, 'w'))
+        keypoint_eval = cocoeval.KeypointEval(ground_truth).evaluate(results, ids)
+        keypoint_eval.summarize()
+        return keypoint_eval
     try:
         from pycocotools.coco import COCO
         from pycocotools.cocoeval import COCOeval
@@ -538,5 +569,8 @@ def validation(args, data_loader=None):
 if __name__ == '__main__':
     logging.basicConfig(level=logging.INFO)
     a = evaluate_cli()
-    kps, ids = run_images(a)
-    print(f'{len(ids)} images, {len(kps)} detections')
+    if a.score:
+        validation(a)
+    else:
+        kps, ids = run_images(a)
+        print(f'{len(ids)} images, {len(kps)} detections')
