@@ -672,6 +672,77 @@ int og_oks_match_i32(const double *oks, const int32_t *det_off, const int32_t *g
                      int A, const double *thresholds, int T, int I, int D, int G, int64_t n_pairs, int32_t *dt_match,
                      unsigned char *dt_ignore, unsigned char *gt_ignore_a, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mask_miss / mask_all from COCO annotations (data/dataset.py:136-197, CocoKeypoints.mask_mask, which calls pycocotools'
+ * annToMask; offsetguided_amd.data.device_masks) ----  One call builds both masks of a batch of images of different sizes on the
+ * device from the person annotations' polygons and run-length encodings.  The rule below has the shape of pycocotools' maskApi
+ * (rleFrPoly, rleDecode); bit parity with pycocotools is NOT claimed (absent from the build): what is pinned is this text and its
+ * numpy restatement tests/coco_mask_common.py, which is written in the sort-and-merge run-length form.
+ * A mask plane of an h x w image is the flat COLUMN-MAJOR bit string a = x h + y, 0 <= a < h w.  Every source contributes toggle
+ * positions; bit a of the plane is the XOR of the toggles at positions <= a.  The parity runs across column ends: a toggle at y = h
+ * of column x is position (x + 1) h; a toggle at h w has no effect.
+ * Polygon of k >= 1 vertices (px_j, py_j), float64.  All arithmetic IEEE double, every product rounded before the sum (no
+ * contraction), (int) truncates toward zero:
+ *   1. X_j = (int)(5 px_j + .5), Y_j = (int)(5 py_j + .5); vertex k is vertex 0.
+ *   2. Edge (xs, ys) -> (xe, ye), j = 0 .. k - 1: dx = |xe - xs|, dy = |ys - ye|; flip = (dx >= dy and xs > xe) or (dx < dy and
+ *      ys > ye); a flipped edge swaps its ends.  dx >= dy: s = (double)(ye - ys) / dx, the edge emits the dx + 1 points (u, v) =
+ *      (xs + t, (int)(ys + s t + .5)) with t running 0 .. dx, or dx .. 0 when flipped.  Otherwise the same along y: s = (double)(xe -
+ *      xs) / dy, (u, v) = ((int)(xs + s t + .5), ys + t).  dx = dy = 0: the one point (xs, ys).  The points of all edges form ONE
+ *      sequence in edge order.
+ *   3. Every consecutive pair (u', v'), (u, v) of that sequence, across edge boundaries too, with u != u': xd = u < u' ? u : u - 1;
+ *      xd = (xd + .5) / 5 - .5; the pair is skipped unless xd is an integer in [0, w - 1]; yd = min(v, v'); yd = (yd + .5) / 5 - .5,
+ *      clamped to [0, h], then ceil; toggle at xd h + yd.
+ * RLE: `cums` = the cumulative sums of the run lengths (column-major runs, the first a 0-run); a toggle at every cumulative sum (a
+ * zero-length run toggles twice at one place).  The host takes the sums, and decodes a compressed `counts` string first.
+ * Annotation mask = the OR of its polygons' planes, or its RLE's plane.  Composition per pixel over the image's annotations in
+ * list order: persons = OR of every non-crowd mask; miss = OR of the non-crowd masks flagged OG_COCO_MISS (num_keypoints <= 0 or
+ * area <= 32 * 32, decided by the host); a crowd annotation at list position c adds crowd' = its mask AND NOT (the OR of the
+ * non-crowd masks listed before c); mask_miss = 255 NOT (miss OR crowd'), mask_all = 255 (persons OR crowd').  (The reference raises
+ * on a second crowd annotation; here every crowd adds its own crowd'.)  An image without annotations: mask_miss 255, mask_all 0.
+ * Tables: one packed buffer, present twice -- tables_host, the bytes as the host wrote them (read by the validation below; pinned or
+ * not), and tables_dev, the same bytes on the device (16-byte aligned).  Sections at byte offsets *_at (multiples of 16): images
+ * OgCocoImage[n_images]; anns OgCocoAnn[n_anns], image by image; pieces OgCocoPiece[n_pieces], annotation by annotation (a piece =
+ * one polygon or one RLE = one bit plane of (h w + 31) / 32 words in the workspace, word_off the running sum); vertices
+ * double[2 n_vertices] rows (x, y); cums uint32[n_cums].  Outputs: row-major (h, w) uint8 planes, 0 / 255, image i at byte
+ * out_off of mask_miss and of mask_all (device, out_bytes each; mask_all may be NULL) -- the masks / offsets form
+ * og_warp_affine_mask_u8 takes.  Four launches (zero the planes, toggle with vector atomic XOR on words -- order-independent, so
+ * deterministic --, fill by an in-word shift-XOR prefix and a wave ballot / LDS carry scan, compose one thread per pixel); without
+ * pieces only the last.  No allocation, no synchronisation, graph-capturable.
+ * og_coco_mask_workspace_bytes: host arithmetic on the descriptor and tables_host (0 for a descriptor og_coco_masks_u8 would refuse).
+ * OG_EINVAL (nothing launched): a null pointer; a descriptor of another size; n_images outside 1..65535, a negative count; a
+ * section that is misaligned or leaves table_bytes; a non-positive h or w, h w beyond 2^28; planes that leave out_bytes;
+ * annotations / pieces / planes that are not consecutive; a piece whose image is not its annotation's; a polygon with fewer than 1
+ * vertex, a non-finite vertex, a coordinate beyond 2^20 in magnitude; RLE runs that are negative or do not sum to h w.
+ * OG_ENOSPC: workspace_bytes too small. */
+#define OG_COCO_POLYGON 0
+#define OG_COCO_RLE 1
+#define OG_COCO_CROWD 1    /* OgCocoAnn.flags: iscrowd */
+#define OG_COCO_MISS 2     /* OgCocoAnn.flags: a person the losses must not see (no keypoints, or area <= 32 * 32) */
+typedef struct OgCocoImage {
+    int64_t out_off;
+    int32_t h, w, ann_first, n_anns;
+} OgCocoImage;
+typedef struct OgCocoAnn {
+    int32_t piece_first, n_pieces, flags, reserved;
+} OgCocoAnn;
+typedef struct OgCocoPiece {
+    int64_t word_off;
+    int32_t image, kind, first, count;   /* first / count: rows of `vertices` (polygon) or entries of `cums` (RLE) */
+} OgCocoPiece;
+typedef struct OgCocoMaskDesc {
+    uint32_t size;             /* sizeof(OgCocoMaskDesc): anything else is refused (OG_EINVAL, "descriptor size") */
+    int32_t n_images, n_anns, n_pieces, n_vertices, n_cums;
+    const void *tables_host;
+    const void *tables_dev;
+    size_t table_bytes;
+    size_t images_at, anns_at, pieces_at, vertices_at, cums_at;
+    unsigned char *mask_miss;
+    unsigned char *mask_all;
+    size_t out_bytes;
+    int32_t stages;            /* 0: every launch; else the launches to queue, 1 zero | 2 toggle | 4 fill | 8 compose (for timing them one by one) */
+} OgCocoMaskDesc;
+size_t og_coco_mask_workspace_bytes(const OgCocoMaskDesc *desc);
+int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

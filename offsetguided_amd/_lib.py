@@ -31,6 +31,16 @@ class LimbsDesc(C.Structure):
         super().__init__(size=C.sizeof(LimbsDesc), **{k: v.data_ptr() if isinstance(v, torch.Tensor) else v for k, v in fields.items()})
 
 
+class CocoMaskDesc(C.Structure):
+    """OgCocoMaskDesc (include/og_decoder.h), field for field.  CocoMaskDesc(name=value, ...) sets `size`; a tensor stands for its pointer."""
+    _fields_ = [("size", C.c_uint32), ("n_images", C.c_int32), ("n_anns", C.c_int32), ("n_pieces", C.c_int32), ("n_vertices", C.c_int32),
+                ("n_cums", C.c_int32), ("tables_host", _vp), ("tables_dev", _vp), ("table_bytes", _sz), ("images_at", _sz), ("anns_at", _sz),
+                ("pieces_at", _sz), ("vertices_at", _sz), ("cums_at", _sz), ("mask_miss", _vp), ("mask_all", _vp), ("out_bytes", _sz), ("stages", C.c_int32)]
+
+    def __init__(self, **fields):
+        super().__init__(size=C.sizeof(CocoMaskDesc), **{k: v.data_ptr() if isinstance(v, torch.Tensor) else v for k, v in fields.items()})
+
+
 # name -> (restype, argtypes); mirrors include/og_decoder.h one to one
 SIGNATURES = {
     "og_abi_version": (_i, []),
@@ -111,6 +121,8 @@ SIGNATURES = {
     "og_oks_matrix_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_int64, _vp, _vp]),
     "og_oks_match_workspace_bytes": (_sz, [_i, _i, _i]),
     "og_oks_match_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "og_coco_mask_workspace_bytes": (_sz, [C.POINTER(CocoMaskDesc)]),
+    "og_coco_masks_u8": (_i, [C.POINTER(CocoMaskDesc), _vp, _sz, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures
@@ -145,7 +157,7 @@ def load():
             raise ImportError(f"{LIB_PATH}: ABI version {lib.og_abi_version()} != {ABI_VERSION}; rebuild with "
                               "`python -m offsetguided_amd.build --force`")
         for name, (res, args) in SIGNATURES.items():
-            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32, og_oks_*: the ABI only grew) -- a library built before
+            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32, og_oks_*, og_coco_*: the ABI only grew) -- a library built before
             # them says so here instead of with a bare AttributeError
             if not hasattr(lib, name):
                 raise ImportError(f"{LIB_PATH} lacks {name}: stale build; rebuild with `python -m offsetguided_amd.build --force`")

@@ -34,23 +34,31 @@ def load_ground_truth(annotation_file):
     """The person annotations of a COCO keypoint file, per image and in file order:
     {image_id: {'keypoints' (g, 17, 3) float64, 'area' (g,) float64, 'bbox' (g, 4) float64, 'iscrowd' (g,) uint8, 'num_keypoints' (g,)
     int64}}.  Every image of the file's `images` list has an entry (g may be 0)."""
+    return {image_id: annotation_arrays(anns) for image_id, anns in person_annotations(annotation_file)[1].items()}
+
+
+def person_annotations(annotation_file):
+    """The parsing load_ground_truth and data.load_annotations share: (the file's `images` list, {image_id: its person annotation
+    dicts in file order}); every image of the list has an entry."""
     with open(annotation_file) as f:
         data = json.load(f)
     rows = {im['id']: [] for im in data.get('images', [])}
     for ann in data.get('annotations', []):
         if ann.get('category_id', 1) == 1:
             rows.setdefault(ann['image_id'], []).append(ann)
-    out = {}
-    for image_id, anns in rows.items():
-        kp = np.array([a['keypoints'] for a in anns], np.float64).reshape(len(anns), K, 3)
-        out[image_id] = {
-            'keypoints': kp,
-            'area': np.array([a['area'] for a in anns], np.float64),
-            'bbox': np.array([a['bbox'] for a in anns], np.float64).reshape(len(anns), 4),
-            'iscrowd': np.array([a.get('iscrowd', 0) for a in anns], np.uint8),
-            'num_keypoints': np.array([a.get('num_keypoints', int((k[:, 2] > 0).sum())) for a, k in zip(anns, kp)], np.int64),
-        }
-    return out
+    return data.get('images', []), rows
+
+
+def annotation_arrays(anns):
+    """One image's person annotation dicts -> the arrays of load_ground_truth's entry."""
+    kp = np.array([a['keypoints'] for a in anns], np.float64).reshape(len(anns), K, 3)
+    return {
+        'keypoints': kp,
+        'area': np.array([a['area'] for a in anns], np.float64),
+        'bbox': np.array([a['bbox'] for a in anns], np.float64).reshape(len(anns), 4),
+        'iscrowd': np.array([a.get('iscrowd', 0) for a in anns], np.uint8),
+        'num_keypoints': np.array([a.get('num_keypoints', int((k[:, 2] > 0).sum())) for a, k in zip(anns, kp)], np.int64),
+    }
 
 
 def _device():

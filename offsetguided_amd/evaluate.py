@@ -59,6 +59,10 @@ def evaluate_cli(argv=None):
                              'it imports, the native scorer cocoeval.KeypointEval otherwise)')
     parser.add_argument('--annotation-file', default=None, type=str,
                         help="COCO keypoint annotations --score reads (default: the --dataset's own file)")
+    parser.add_argument('--image-dir', default=None, type=str,
+                        help="read the images from this directory (data.CocoKeypoints on the annotation file when it exists, data.ImageList "
+                             "of the directory's files otherwise) instead of the synthetic stand-in; decoded by PIL, rescaled, padded and "
+                             'normalised on the device')
     parser.add_argument('--loader-workers', default=8, type=int)
     parser.add_argument('--all-images', default=False, action='store_true')
     parser.add_argument('--resume', '-r', action='store_true', default=False, help='load --checkpoint-whole')
@@ -89,9 +93,11 @@ def evaluate_cli(argv=None):
         validate_views(args)
     except ValueError as e:
         parser.error(str(e))
-    args.image_dir, annotation_file = {
+    args.raw_image_dir = args.image_dir       # only an explicit --image-dir makes run_images read files
+    default_dir, annotation_file = {
         'val': (IMAGE_DIR_VAL, ANNOTATIONS_VAL), 'test': (IMAGE_DIR_TEST, ANNOTATIONS_TEST),
         'test-dev': (IMAGE_DIR_TEST, ANNOTATIONS_TESTDEV)}[args.dataset]
+    args.image_dir = args.image_dir or default_dir
     args.annotation_file = args.annotation_file or annotation_file
     if args.dataset in ('test', 'test-dev'):
         args.all_images = True
@@ -199,6 +205,19 @@ def synthetic_loader(n_batches, batch_size, size, device, seed=0):
         yield images, [None] * batch_size, metas
 
 
+def image_dir_loader(args):
+    """--image-dir: batches of raw (h, w, 3) uint8 images for run_images' device input chain -- data.CocoKeypoints when the annotation
+    file exists (the reference's id filtering, --all-images for every image), data.ImageList of the directory's files otherwise (image
+    ids = positions in the sorted listing)."""
+    from . import data
+    if getattr(args, 'annotation_file', None) and os.path.exists(args.annotation_file):
+        dataset = data.CocoKeypoints(args.raw_image_dir, args.annotation_file, all_images=getattr(args, 'all_images', False))
+    else:
+        names = sorted(f for f in os.listdir(args.raw_image_dir) if f.lower().endswith(('.jpg', '.jpeg', '.png', '.bmp', '.ppm')))
+        dataset = data.ImageList([os.path.join(args.raw_image_dir, f) for f in names])
+    return data.raw_batches(dataset, args.batch_size)
+
+
 ENGINE_CACHE = 8     # input shapes run_images keeps engines for (--fixed-height: one per padded width, a handful on COCO; an engine
                      # holds its activations + graph, ~0.1 GB per image of 640x640, the weights are shared)
 # Batches in flight: batch i runs whole (backbone graph + decoder) on HIP stream i % IN_FLIGHT with that lane's PostProcess; the head
@@ -226,6 +245,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                                           drop_layers=False, load_amp=False)
     processors = [decoder.decoder_factory(args) for _ in range(IN_FLIGHT)]
     lanes = _lib.lane_streams(dev, IN_FLIGHT) if IN_FLIGHT > 1 else [torch.cuda.current_stream(dev)]
+    if data_loader is None and getattr(args, 'raw_image_dir', None):
+        data_loader = image_dir_loader(args)
     if data_loader is None:
         data_loader = synthetic_loader(n_synthetic_batches, args.batch_size, args.long_edge, dev)
     feeder = DeviceFeeder(dev)

@@ -50,6 +50,10 @@ def train_cli(argv=None):
     g.add_argument('--augment', action='store_true', default=False,
                    help='augment on the device: raw uint8 images + annotations in the pool, a new random WarpAffineTransforms crop '
                         '(flip, rotate, scale, stretch, translate) of every batch in every step')
+    g.add_argument('--train-annotations', default=None, type=str, metavar='FILE',
+                   help='train on a COCO keypoint annotation file (data.CocoKeypoints; with --train-image-dir, implies --augment): '
+                        'mask_miss is rasterised on the device from the polygons and RLEs and carried through the warp into the losses')
+    g.add_argument('--train-image-dir', default=None, type=str, metavar='DIR', help="directory of that file's images")
     g.add_argument('--flip-prob', default=0.5, type=float, help='the probability to flip the input image')
     g.add_argument('--max-rotate', default=45, type=float, help='upper bound of the image rotation during augmentation')
     g.add_argument('--min-scale', default=0.5, type=float, help='lower bound of the relative image scale during augmentation')
@@ -71,7 +75,12 @@ def train_cli(argv=None):
     g.add_argument('--learning-rate', type=float, default=2.5e-4, help='learning rate for world size 1')
     g.add_argument('--momentum', default=0.9, type=float)
     g.add_argument('--weight-decay', '--wd', default=0, type=float)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if bool(args.train_annotations) != bool(args.train_image_dir):
+        p.error('--train-annotations and --train-image-dir go together')
+    if args.train_annotations:
+        args.augment = True
+    return args
 
 
 def synthetic_targets(seed, batch, size, device, *, background=False, jitter=False, scale=False):
@@ -137,24 +146,54 @@ def synthetic_raw_images(seed, joints, n_persons, height, width):
 
 def augmented_batch(augment, entry, rng, events=None):
     """One training batch from a pool entry of raw images + annotations: a new random crop (transforms.DeviceAugment) -> (images,
-    (joints, n_persons)) on the device.  events: a list that receives a (start, end) pair of HIP timing events round the augment calls."""
-    raws, joints, n_persons, n_persons_dev = entry
+    (joints, n_persons)) on the device.  events: a list that receives a (start, end) pair of HIP timing events round the augment calls.
+    An entry with a fifth element (annotations.MaskTables, from a COCO file) has its mask_miss built on the device (data.device_masks)
+    and warped with the images: -> (images, (joints, n_persons, mask (N,S,S) uint8))."""
+    raws, joints, n_persons, n_persons_dev = entry[:4]
     stream = torch.cuda.current_stream(augment.device)
     if events is not None:
         start, end = _lib.TimingEvent(), _lib.TimingEvent()
         start.record(stream)
-    images, joints_dev, _, _ = augment(raws, joints, n_persons, rng=rng)
+    if len(entry) > 4:
+        from . import data
+        images, joints_dev, mask, _ = augment(raws, joints, n_persons, data.device_masks(entry[4], augment.device, mask_all=False), rng=rng)
+    else:
+        images, joints_dev, _, _ = augment(raws, joints, n_persons, rng=rng)
     if events is not None:
         end.record(stream)
         events.append((start, end))
+    if len(entry) > 4:
+        return images.contiguous(memory_format=torch.channels_last), (joints_dev, n_persons_dev, mask)
     return images.contiguous(memory_format=torch.channels_last), (joints_dev, n_persons_dev)
 
 
-def encode_targets(encoders, joints, n_persons):
+def coco_pool(args, rank, world, dev):
+    """The pool of --train-annotations: this rank's share of data.CocoKeypoints in batches of --batch-size (a ragged last batch is
+    dropped), every entry (raw images, joints, n_persons, n_persons on the device, mask tables) -- what augmented_batch takes.  The
+    images are decoded once and stay on the host; crop, mask_miss and targets are made on the device in every step."""
+    from . import data
+    dataset = data.CocoKeypoints(args.train_image_dir, args.train_annotations)
+    indices = list(range(rank, len(dataset), world))
+    pool = []
+    for first in range(0, len(indices) - args.batch_size + 1, args.batch_size):
+        raws, joints, n_persons, tables, _ = data.collate_raw([dataset[i] for i in indices[first:first + args.batch_size]])
+        pool.append((raws, joints, n_persons, torch.from_numpy(n_persons).to(dev), tables))
+    if not pool:
+        raise ValueError(f'--train-annotations: {len(indices)} images for rank {rank}, fewer than one batch of {args.batch_size}')
+    return pool
+
+
+def encode_targets(encoders, joints, n_persons, mask_miss=None):
     """Device-side ground truth (offsetguided_amd.encoder = reference encoder/): the same annos layout as
-    synthetic_targets, produced from annotations by the HIP encoder kernels inside the step."""
-    hm, bg, jit, mask = encoders[0].encode_batch(joints, n_persons)
-    off, sc, ps, _ = encoders[1].encode_batch(joints, n_persons)
+    synthetic_targets, produced from annotations by the HIP encoder kernels inside the step.  mask_miss: the warped (N,S,S) uint8
+    mask of the crops (0 = not labelled), shrunk to each head's stride by its encoder (og_shrink_mask_miss_u8); None = all labelled."""
+    if mask_miss is None:
+        hm, bg, jit, mask = encoders[0].encode_batch(joints, n_persons)
+        off, sc, ps, _ = encoders[1].encode_batch(joints, n_persons)
+    else:
+        hm, bg, jit, mask = encoders[0].encode_batch(joints, n_persons, mask_miss)
+        off, sc, ps, omask = encoders[1].encode_batch(joints, n_persons, mask_miss)
+        return [(hm, bg if bg.numel() else None, jit if jit.numel() else None, mask), (off, sc if sc.numel() else None, ps, omask)]
     return [(hm, bg if bg.numel() else None, jit if jit.numel() else None, mask), (off, sc if sc.numel() else None, ps, mask)]
 
 
@@ -264,8 +303,9 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
                        'sync_bn': bool(args.sync_bn and world > 1), 'grad_payload': str(payload_dtype).replace('torch.', '')},
             'grad_allreduce': {'bytes': nbytes, 'ms': comm_ms, 'bus_GBps': bus,
                                'exposed_comm_ms': round(max(step_s - nosync_s, 0.0) * 1e3, 2) if world > 1 else 0.0},
-            'data': 'synthetic raw images, augmented and encoded on the device' if augment is not None
-                    else 'synthetic annotations, GT encoded on the device', **extra}))
+            'data': ('COCO annotations: mask_miss rasterised, images augmented and targets encoded on the device'
+                     if getattr(args, 'train_annotations', None) else 'synthetic raw images, augmented and encoded on the device')
+                    if augment is not None else 'synthetic annotations, GT encoded on the device', **extra}))
     if dist.is_initialized():
         dist.destroy_process_group()
 
@@ -330,7 +370,9 @@ def main(argv=None):
                                        jpeg_quality=args.jpeg_quality, jitter_prob=args.annotation_jitter_prob)
         augment = transforms.DeviceAugment(args.square_length, args, device=dev, photo_params=photo,
                                            np_rng=np.random.RandomState(1000 * rank + 11))
-        for i in range(4):
+        if args.train_annotations:
+            pool = coco_pool(args, rank, world, dev)
+        for i in range(0 if args.train_annotations else 4):
             joints, n_persons = synthetic_annotations(1000 * rank + i, args.batch_size, 480, 640)
             pool.append((synthetic_raw_images(1000 * rank + i, joints, n_persons, 480, 640), joints, n_persons,
                          torch.from_numpy(n_persons).to(dev)))

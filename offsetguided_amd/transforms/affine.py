@@ -124,7 +124,8 @@ def _align16(v):
 class DeviceAugment:
     """Batched WarpAffineTransforms + ToTensor + Normalize.  Called as (raw_images, joints, n_persons, mask_miss=None, rng=random):
     raw_images a list of (h, w, 3) uint8 arrays of any sizes, joints (N,P,17,4) fp32 rows [x, y, v, scale] in source pixels,
-    n_persons (N,) int32, mask_miss a list of (h, w) uint8 arrays of the images' sizes -> (images (N,3,S,S) fp32 normalised, joints
+    n_persons (N,) int32, mask_miss a list of (h, w) uint8 arrays of the images' sizes, or a data.DeviceMasks (the planes
+    og_coco_masks_u8 left in device memory: warped straight from there, nothing of them is staged) -> (images (N,3,S,S) fp32 normalised, joints
     (N,P,17,4), mask (N,S,S) uint8 or None, all on the device; mats (N,3,3) float64 numpy).  Images, masks and annotations are packed
     into one pinned staging buffer and copied once; everything is queued on the current stream and the call never waits for the
     device (a staging buffer whose last copy is still in flight is left alone and a new one is taken).
@@ -188,7 +189,8 @@ class DeviceAugment:
         M = np.ascontiguousarray(np.asarray(mats, np.float64)[:, 0:2])
         img_bytes = sum(h * w * 3 for h, w in sizes)
         mask_at = _align16(img_bytes)
-        mask_bytes = sum(h * w for h, w in sizes) if mask_miss is not None else 0
+        on_device = hasattr(mask_miss, 'buffer') and hasattr(mask_miss, 'offsets')          # data.DeviceMasks
+        mask_bytes = sum(h * w for h, w in sizes) if mask_miss is not None and not on_device else 0
         joints_at = _align16(mask_at + mask_bytes)
         np_at = _align16(joints_at + joints.nbytes)
         total = np_at + n_persons.nbytes
@@ -208,7 +210,11 @@ class DeviceAugment:
             hw4[4 * i:4 * i + 4] = [h, w, 0, 0]
             o += h * w * 3
         moffs, o = (C.c_long * n)(), 0
-        if mask_miss is not None:
+        if on_device:
+            assert list(mask_miss.sizes) == sizes, 'mask_miss: the planes of a DeviceMasks have the images\' sizes'
+            assert mask_miss.buffer.device == dev, 'mask_miss: the DeviceMasks lives on another device'
+            moffs[:] = [int(o) for o in mask_miss.offsets]
+        elif mask_miss is not None:
             assert len(mask_miss) == n
             for i, (m, (h, w)) in enumerate(zip(mask_miss, sizes)):
                 assert m.dtype == np.uint8 and m.shape == (h, w), 'mask_miss: (h, w) uint8 of the image\'s size'
@@ -244,8 +250,8 @@ class DeviceAugment:
         mask = None
         if mask_miss is not None:
             mask = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
-            _lib.check(lib.og_warp_affine_mask_u8(_lib.ptr(dev_raw[mask_at:]), moffs, hw4, n, Dc, S, self.mask_border, _lib.ptr(mask),
-                                                  stream), lib)
+            planes = mask_miss.buffer if on_device else dev_raw[mask_at:]
+            _lib.check(lib.og_warp_affine_mask_u8(_lib.ptr(planes), moffs, hw4, n, Dc, S, self.mask_border, _lib.ptr(mask), stream), lib)
         joints_dev = dev_raw[joints_at:joints_at + joints.nbytes].view(torch.float32).view(joints.shape)
         np_dev = dev_raw[np_at:np_at + n_persons.nbytes].view(torch.int32)
         out_joints = torch.empty(joints.shape, dtype=torch.float32, device=dev)
