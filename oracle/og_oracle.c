@@ -809,9 +809,8 @@ static void ogo_cubic_taps(float x, short *t)
 
 static int ogo_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-static void ogo_resize_cubic_u8_ch(const unsigned char *src, int h, int w, unsigned char *dst, int nh, int nw, int ch)
+static void ogo_resize_cubic_u8_ch(const unsigned char *src, int h, int w, unsigned char *dst, int nh, int nw, int ch, double sy, double sx)
 {
-    const double sx = (double)w / nw, sy = (double)h / nh;
     for (int dy = 0; dy < nh; ++dy) {
         float fy = (float)((dy + 0.5) * sy - 0.5);
         const int y0 = (int)floorf(fy);
@@ -839,14 +838,21 @@ static void ogo_resize_cubic_u8_ch(const unsigned char *src, int h, int w, unsig
 
 OGO_API void ogo_resize_cubic_u8(const unsigned char *src, int h, int w, unsigned char *dst, int nh, int nw)
 {
-    ogo_resize_cubic_u8_ch(src, h, w, dst, nh, nw, 3);
+    ogo_resize_cubic_u8_ch(src, h, w, dst, nh, nw, 3, (double)h / nh, (double)w / nw);   /* dsize given: inv_scale = dsize / ssize */
 }
 
 /* encoder/heatmap.py:56-60, encoder/offset.py:46-50: the full-resolution uint8 mask_miss (h, w), 0 / 255, shrunk by
- * cv2.resize(fx = fy = 1 / stride, INTER_CUBIC), / 255, > 0.7 -> bool (h / stride, w / stride).  float32(v) / 255 > 0.7
- * <=> v >= 179 for integer v.  Same published 8-bit algorithm as above (parity with cv2 itself unpinned). */
-OGO_API void ogo_shrink_mask_miss_u8(const unsigned char *mask, int h, int w, unsigned char *out, int nh, int nw)
+ * cv2.resize(dsize = (0, 0), fx = fy = 1 / stride, INTER_CUBIC), / 255, > 0.7 -> bool.  float32(v) / 255 > 0.7
+ * <=> v >= 179 for integer v.  Same published 8-bit algorithm as above (parity with cv2 itself unpinned).
+ * With an empty dsize cv::resize takes dsize = cvRound(ssize * fx) (round half to even) and KEEPS fx as the inverse scale
+ * (resize.cpp: inv_scale_x is recomputed as dsize / ssize only in the other branch, where dsize is given), so destination
+ * index d maps to (d + 0.5) * stride - 0.5 whether or not the size is a multiple of the stride: nh, nw here are the rounded
+ * sizes, the coordinate scale is 1 / (1 / stride) as cv::resize computes it from the reference's fx = 1 / stride.  That equals
+ * (double)stride -- what og_shrink_mask_miss_u8 passes to its kernel -- for every power of two, the strides in use; it does not for
+ * every integer (49 is the first that differs). */
+OGO_API void ogo_shrink_mask_miss_u8(const unsigned char *mask, int h, int w, unsigned char *out, int nh, int nw, int stride)
 {
-    ogo_resize_cubic_u8_ch(mask, h, w, out, nh, nw, 1);
+    const double scale = 1. / (1. / stride);
+    ogo_resize_cubic_u8_ch(mask, h, w, out, nh, nw, 1, scale, scale);
     for (long i = 0; i < (long)nh * nw; ++i) out[i] = (float)out[i] / 255.f > 0.7f ? 1 : 0;
 }

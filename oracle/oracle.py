@@ -69,7 +69,7 @@ def lib():
                                      _I32, _I32, _I32, C.c_int, _F, _F]
         L.ogo_resize_cubic_u8.argtypes = [np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS"), C.c_int, C.c_int,
                                           np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS"), C.c_int, C.c_int]
-        L.ogo_shrink_mask_miss_u8.argtypes = L.ogo_resize_cubic_u8.argtypes
+        L.ogo_shrink_mask_miss_u8.argtypes = L.ogo_resize_cubic_u8.argtypes + [C.c_int]
         L.ogo_group_stats.argtypes = [np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS"), C.c_int]
         _lib = L
     return _lib
@@ -250,12 +250,13 @@ def resize_cubic_u8(img, new_h, new_w):
 
 
 def shrink_mask_miss_u8(mask, stride):
-    """encoder/heatmap.py:56-60: (h, w) uint8 mask_miss -> bool (h // stride, w // stride) = cv2.resize(fx = 1 / stride, INTER_CUBIC)
-    / 255 > 0.7 (PARITY UNPINNED against cv2, like resize_cubic_u8)."""
+    """encoder/heatmap.py:56-60: (h, w) uint8 mask_miss -> bool (round(h / stride), round(w / stride)), halves to even, =
+    cv2.resize(dsize=(0, 0), fx = 1 / stride, INTER_CUBIC) / 255 > 0.7: the coordinate scale is the stride itself, also where it does
+    not divide the size (PARITY UNPINNED against cv2, like resize_cubic_u8)."""
     mask = np.ascontiguousarray(mask, np.uint8)
     nh, nw = int(round(mask.shape[0] / stride)), int(round(mask.shape[1] / stride))
     out = np.empty((nh, nw), np.uint8)
-    lib().ogo_shrink_mask_miss_u8(mask, mask.shape[0], mask.shape[1], out, nh, nw)
+    lib().ogo_shrink_mask_miss_u8(mask, mask.shape[0], mask.shape[1], out, nh, nw, int(stride))
     return out.astype(bool)
 
 

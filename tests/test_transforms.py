@@ -129,8 +129,10 @@ def test_resize_and_fused_chain_bit_exact_vs_restatement():
 @pytest.mark.gpu
 def test_batched_input_chain_equals_per_image_launches():
     """og_rescale_pad_normalize_batch_u8 (one launch per batch, evaluate.py:157-182) == og_rescale_pad_normalize_u8 per image, bit for
-    bit: mixed sizes incl. a 4.7x reduction (the tile footprint exceeds the LDS image: direct path) and an enlargement, both
-    paddings, and more images than one launch's descriptor table holds (64)."""
+    bit: mixed sizes incl. a 4.7x reduction (3000 x 2000 -> 640 x 426: the footprint estimate is 308 x 26 x 3 = 24 024 bytes, still
+    the LDS path), a 5.2x one (3300 x 2200: 338 x 28 x 3 bytes, the direct path; tests/input_chain_common.takes_lds restates the
+    decision) and an enlargement, both paddings, and more images than one launch's descriptor table holds (64).  Both entries share the
+    tile function: what holds them to an independent reference is tests/test_gpu_input_chain.py."""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected but no HIP device is visible")
     import ctypes as C
@@ -140,7 +142,7 @@ def test_batched_input_chain_equals_per_image_launches():
     rng = np.random.default_rng(11)
     f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])  # noqa: E731
     mean, std, fill = f3(data_mean), f3(data_std), f3(transforms.pad.FILL)
-    for T, fixed, sizes in ((640, False, [(427, 640), (640, 480), (3000, 2000), (97, 131), (640, 640)]),
+    for T, fixed, sizes in ((640, False, [(427, 640), (640, 480), (3000, 2000), (3300, 2200), (97, 131), (640, 640)]),
                             (128, False, [(31 + i, 17 + 2 * i) for i in range(70)]),
                             (256, True, [(300, 400), (150, 200), (600, 800)])):
         images = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in sizes]
