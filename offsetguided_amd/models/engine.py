@@ -4,10 +4,11 @@ What this file adds to the eager module is the shape the hardware wants:
   * every BatchNorm folded into the preceding convolution (160 BN layers disappear);
   * fp16 (default: the reference's apex-O2 arithmetic) or bf16 activations / weights in channels-last (NHWC) layout;
   * EVERY convolution on a hand-written MFMA kernel, bias + ReLU + residual add fused into its epilogue, fp32 accumulation:
-    og_conv3x3_tiled_* / og_conv3x3s2_tiled_* / og_conv1x1_tiled_* for the 160x160 ... 20x20 levels (two 4-wave workgroups
-    per CU, pre-tiled weights), the band-resident og_conv_band_* (K split inside a workgroup, no slabs) for 10x10 / 5x5, the
-    split-K kernel og_conv2d_* / og_conv2d_proj_* for the stride-2 / projection layers at 20x20 and whatever the band kernel does
-    not serve, og_stem7x7_* for the stem, og_conv1x1_heads_* for the heads;
+    og_conv3x3_tiled_* / og_conv3x3s2_tiled_* / og_conv1x1_tiled_* (two 4-wave workgroups per CU, pre-tiled weights) for the large
+    levels, the band-resident og_conv_band_* (K split inside a workgroup, no slabs) for the smallest, the split-K kernel
+    og_conv2d_* / og_conv2d_proj_* in between, og_stem7x7_* for the stem, og_conv1x1_heads_* for the heads.  WHICH of them serves a
+    layer is decided by _Conv.route and, for a block (does the 1x1 projection ride on conv2?), _Residual.route, nowhere else: shapes
+    in, a launcher's name out, no GPU needed (tests/test_engine_route_cpu.py tabulates them); the thresholds are the constants below;
     a shape none of them serves RAISES (InferenceEngine(strict=True), the default on the 16-bit GPU engines); with strict=False it
     runs on torch's convolution + one og_bias_act_* pass and is listed in engine.torch_conv_calls;
   * the hourglass merges (nearest x2 upsample + add) on the epilogue of the convolution below them where that kernel is the
@@ -29,16 +30,16 @@ depth >= 2), OG_ENGINE_DEEP_SHARED (3: the inner up1 branches in fork order on o
 band-resident kernel for 10x10 / 5x5), OG_ENGINE_WHATIF (timing diagnosis, wrong results).  The experiments that lost their A/B (branch delay, shared side stream, stream priorities, ...) are described in
 EXPERIMENTS.md and no longer exist as switches.
 """
+import ctypes as C
 import os
 import threading
+import weakref
 
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
 from .hourglass_104 import ConvBlock, HourglassLevel, Residual
-
-
 
 
 def _fold(conv, bn):
@@ -55,14 +56,22 @@ def _fold(conv, bn):
     return w, b
 
 
+def _is_cl(t):
+    return t.is_contiguous(memory_format=torch.channels_last)
+
+
+def _cl(t):
+    """t as a channels-last contiguous tensor: itself where it is one (or None), else a copy."""
+    return t if t is None or _is_cl(t) else t.contiguous(memory_format=torch.channels_last)
+
+
 def _epilogue(y, bias32, bias_lp, skip, relu, fused):
     """y = act(y + bias (+ skip)) in place.  fused: one hand-written HIP pass (og_bias_act_bf16);
     otherwise plain torch ops (CPU / fp32 checking path)."""
     if fused:
         n, c, h, w = y.shape
-        assert y.is_contiguous(memory_format=torch.channels_last) and (skip is None or skip.shape == y.shape)
-        if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-            skip = skip.contiguous(memory_format=torch.channels_last)
+        assert _is_cl(y) and (skip is None or skip.shape == y.shape)
+        skip = _cl(skip)
         lib = _lib.load()
         _lib.check(_lib.lp(lib, 'og_bias_act', y.dtype)(_lib.ptr(y), _lib.ptr(bias32), _lib.ptr(skip) if skip is not None else None,
                                         n * h * w, c, int(relu), _lib.stream_ptr(y.device)), lib)
@@ -117,6 +126,8 @@ CONV_WARM_NEXT = int(os.environ.get('OG_CONV_WARM_NEXT', '1'))
 CONV_UP2 = int(os.environ.get('OG_CONV_UP2', '1'))   # the hourglass merge (upsample x2 + add) on the epilogue of the convolution below it
 _conv_ws = {}
 _WHATIF = set(filter(None, os.environ.get('OG_ENGINE_WHATIF', '').split(',')))
+
+
 class _Issuer(threading.local):
     """Who is issuing work on THIS host thread (engines may be built / run from several threads and on several
     streams): the engine id and the concurrent branch (0 = trunk, d+1 = up1 branch of level d) select the scratch."""
@@ -126,10 +137,11 @@ class _Issuer(threading.local):
     ws = None             # the issuing engine's scratch buffers (None: a bare _Conv call outside an engine -> the module's _conv_ws)
     eng = None            # the InferenceEngine whose forward is being issued (strict mode, torch_conv_calls)
     names = None          # id(conv module) -> qualified name, while an engine's layers are being built
+    deep_side = None      # ((device, engine), stream): the side stream the deep levels of that engine share (_Level)
 
 
 _issuer = _Issuer()
-_live_engines = __import__('weakref').WeakValueDictionary()      # engine id -> InferenceEngine, while it exists
+_live_engines = weakref.WeakValueDictionary()      # engine id -> InferenceEngine, while it exists
 
 
 def _torch_conv(name, x, weight, stride=1, padding=0):
@@ -163,7 +175,8 @@ def _release_side(stream, key):
 
 
 def _conv3x3_workspace(device, nbytes):
-    """One zero-initialised scratch per (engine, device, concurrent branch) for og_conv3x3_bf16 (zero page + split-K slabs).
+    """One zero-initialised scratch per (engine, device, concurrent branch) for the kernels that split K across
+    workgroups (og_conv2d_* / og_conv2d_proj_*, og_conv3x3_tiled_* at the 40- and 20-wide levels: zero page, tickets, fp32 slabs).
     Layers of one branch run back to back on one stream, so they share it; it only ever grows outside graph capture.  The
     buffers belong to the ENGINE that issues the work (_issuer.ws = InferenceEngine._ws) and go with it: a process-wide cache keyed
     by engine id kept ~17 MB per engine ever built (run_images --fixed-height builds one per new width)."""
@@ -207,62 +220,97 @@ class _Conv:
         Classes: s2big (large stride-2 3x3), 1x1 (pointwise), chain (the small levels), c160 / c80 / c40 (tiled 3x3 by level)."""
         if not _WHATIF:
             return None
-        n, c, h, w = x.shape
-        st, k = self.stride[0], self.w.shape[2]
-        ho, wo = (h - 1) // st + 1, (w - 1) // st + 1
-        pixels = n * ho * wo
+        n, cout, ho, wo = self.out_shape(x.shape)
+        st, k, pixels = self.stride[0], self.w.shape[2], n * ho * wo
         cls = ('1x1' if k == 1 else 'chain' if pixels <= CONV3X3_MAX_PIXELS else 's2big' if st == 2 else
                'c160' if ho >= 160 else 'c80' if ho >= 80 else 'c40')
         if cls not in _WHATIF:
             return None
-        return torch.empty((n, self.w.shape[0], ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        return torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+
+    def out_shape(self, x_shape):
+        """(N, Cout, Hout, Wout) for an input of x_shape (3x3 with pad 1 and 1x1 with pad 0: ceil(H / stride))."""
+        n, _, h, w = x_shape
+        st = self.stride[0]
+        return n, self.w.shape[0], (h - 1) // st + 1, (w - 1) // st + 1
+
+    def pixels(self, x_shape):
+        n, _, ho, wo = self.out_shape(x_shape)
+        return n * ho * wo
+
+    def route(self, x_shape, dtype, on_gpu, channels_last=True, x2_shape=None, proj=None, merge=False):
+        """The kernel that serves this layer on an input of x_shape, from shapes alone: 'band' | 'tiled' | 'up2' | 'splitk' |
+        'tiled_s2' | 'torch', each its launcher's name.  proj, x2_shape: the block's 1x1 projection (residual.skip) of an input of
+        x2_shape is offered to ride along K: 'band+proj' | 'splitk+proj' where it does, else the layer's own route.  merge: the
+        hourglass merge is offered for the epilogue ('up2').  THE place that reads the kernel-selecting knobs (when called) and
+        asks the library what its kernels serve."""
+        if not self.hip3x3:
+            return 'torch'
+        n, c, h, w = x_shape
+        cout, st = self.w.shape[0], self.stride[0]
+        pixels = self.pixels(x_shape)
+        lib = _lib.load()
+        small = (CONV_BAND_MAX_PIXELS and not _WHATIF and on_gpu and dtype == self.w.dtype and c == self.w.shape[1]
+                 and pixels <= CONV_BAND_MAX_PIXELS)
+
+        def band(h2=0, w2=0, c2=0, st2=1):
+            # one round of workgroups: a layer cut into more bands than that (stride 2 from 20x20: 576) is slower than the split-K kernel
+            return 0 < lib.og_conv_band_supported(n, h, w, c, cout, st, h2, w2, c2, st2) <= 320
+        if proj is not None:
+            if (small and x2_shape is not None and tuple(proj.w.shape[2:]) == (1, 1) and tuple(proj.pad) == (0, 0)
+                    and band(x2_shape[2], x2_shape[3], x2_shape[1], proj.stride[0])):
+                return 'band+proj'
+            if self.w_alt is not None and pixels <= CONV3X3_MAX_PIXELS and not _WHATIF:      # [w | projection], _Residual.w_cat
+                return 'splitk+proj'
+        # (Cout % 128 and the tile shapes: tiled_kind() in csrc/conv3x3_tiled.inc)
+        tiled = (st == 1 and (CONV_TILED & 1) and pixels >= CONV_TILED_MIN_PIXELS
+                 and lib.og_conv3x3_tiled_supported(n, h, w, c, cout))
+        # a merge is taken before the band kernel is asked (they meet only where CONV_BAND_MAX_PIXELS >= CONV_TILED_MIN_PIXELS); 2^30:
+        # the (N, Cout, 2H, 2W) tensor it updates in place
+        if tiled and merge and CONV_UP2 and not _WHATIF and on_gpu and n * h * w * 4 * cout < 2 ** 30:
+            return 'up2'
+        if small and band():
+            return 'band'
+        if tiled:
+            return 'tiled'
+        if pixels <= (CONV_S2_MAX_PIXELS if st == 2 else CONV3X3_MAX_PIXELS):
+            return 'splitk'
+        if st == 2 and (CONV_TILED & 2) and channels_last and lib.og_conv3x3s2_tiled_supported(n, h, w, c, cout):
+            return 'tiled_s2'
+        if pixels <= CONV_SPLITK_LAST_RESORT:      # a shape no tiled kernel serves (e.g. the 20-wide level of 24 images): still ours
+            return 'splitk'
+        return 'torch'
+
+    def pointwise_ok(self, x_shape, on_gpu, channels_last=True, x2_shape=None):
+        """This 1x1 layer can run on og_conv1x1_tiled_* (large levels, channel multiples the kernel serves) for an input of x_shape
+        [+ a second input of x2_shape through a second layer: the junction between the stacks]."""
+        return bool((CONV_TILED & 4) and not _WHATIF and self.fused and tuple(self.w.shape[2:]) == (1, 1) and tuple(self.pad) == (0, 0)
+                    and x_shape[1] % 64 == 0 and self.w.shape[0] % 128 == 0 and on_gpu and channels_last
+                    and self.pixels(x_shape) >= CONV_PW_MIN_PIXELS and (x2_shape is None or tuple(x2_shape) == tuple(x_shape)))
 
     def __call__(self, x, skip=None):
+        """act(conv(x) + bias (+ skip)) on the launcher that route() names."""
         fake = self._whatif_skipped(x)
         if fake is not None:
             return fake
-        n, c, h, w = x.shape
-        if self.hip3x3:
-            st = self.stride[0]
-            pixels = n * ((h - 1) // st + 1) * ((w - 1) // st + 1)
-            if self.band_ok(x):
-                return self.band(x, skip)
-            # 3x3 stride 1 on the tiled kernel where it serves the shape, the small levels (and the small stride-2 layers) on the
-            # split-K kernel
-            if (st == 1 and (CONV_TILED & 1) and pixels >= CONV_TILED_MIN_PIXELS and self.w.shape[0] % 128 == 0
-                    and _lib.load().og_conv3x3_tiled_supported(n, h, w, c, self.w.shape[0])):
-                return self._hip(x, skip)
-            if pixels <= (CONV_S2_MAX_PIXELS if st == 2 else CONV3X3_MAX_PIXELS):
-                return self._hip(x, skip)
-            if (st == 2 and (CONV_TILED & 2) and x.is_contiguous(memory_format=torch.channels_last)
-                    and _lib.load().og_conv3x3s2_tiled_supported(n, h, w, c, self.w.shape[0])):
-                if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-                    skip = skip.contiguous(memory_format=torch.channels_last)
-                return self._tiled_s2(x, skip)
-            if pixels <= CONV_SPLITK_LAST_RESORT:      # a shape no tiled kernel serves (e.g. the 20-wide level of 24 images): still ours
-                return self._hip(x, skip)
-        return _epilogue(self.raw(x), self.b32, self.b, skip, self.relu, self.fused)
+        how = self.route(tuple(x.shape), x.dtype, x.is_cuda, _is_cl(x))
+        if how == 'torch':
+            return _epilogue(self.raw(x), self.b32, self.b, skip, self.relu, self.fused)
+        return {'band': self.band, 'tiled': self._tiled, 'splitk': self._splitk, 'tiled_s2': self._tiled_s2}[how](x, skip)
 
-    def band_ok(self, x, x2=None, proj=None):
-        """This 3x3 layer (+ the 1x1 projection `proj` of x2, residual.skip) can run on og_conv_band_* for input x."""
-        return x.is_cuda and self.band_ok_shape(tuple(x.shape), tuple(x2.shape) if x2 is not None else None, proj, x.dtype)
-
-    def band_ok_shape(self, x_shape, x2_shape, proj, dtype):
-        if not (CONV_BAND_MAX_PIXELS and self.hip3x3 and dtype == self.w.dtype) or _WHATIF:
-            return False
-        n, c, h, w = x_shape
-        st = self.stride[0]
-        if c != self.w.shape[1] or n * ((h - 1) // st + 1) * ((w - 1) // st + 1) > CONV_BAND_MAX_PIXELS:
-            return False
-        h2 = w2 = c2 = 0
-        st2 = 1
-        if proj is not None:
-            if tuple(proj.w.shape[2:]) != (1, 1) or tuple(proj.pad) != (0, 0) or x2_shape is None:
-                return False
-            _, c2, h2, w2 = x2_shape
-            st2 = proj.stride[0]
-        # one round of workgroups: a layer cut into more bands than that (stride 2 from 20x20: 576) is slower than the split-K kernel
-        return 0 < _lib.load().og_conv_band_supported(n, h, w, c, self.w.shape[0], st, h2, w2, c2, st2) <= 320
+    def _packed(self, order, other=None):
+        """w_tiled: the weights in the layout `order` of the tiled kernels (0: 3x3 stride 1, 1: 3x3 stride 2, 2: 1x1 [+ the weights of
+        `other`, the junction's second layer, along K]), packed on first use (the warm-up passes, never inside graph capture)."""
+        if self.w_tiled is None:
+            assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
+            lib = _lib.load()
+            cout, src = self.w.shape[0], self.w
+            if order == 2:
+                src = src.reshape(cout, -1) if other is None else torch.cat([src.reshape(cout, -1), other.w.reshape(cout, -1)], 1)
+                src = src.contiguous()
+            self.w_tiled = torch.empty(src.numel(), dtype=src.dtype, device=src.device)
+            _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(src), src.shape[1], cout, order, _lib.ptr(self.w_tiled), _lib.stream_ptr(src.device)), lib)
+        return self.w_tiled
 
     def band_pack(self, device, proj=None):
         """The layer's weights (+ the projection's) in og_conv_band_*'s fragment order, packed once (never inside graph capture)."""
@@ -280,93 +328,6 @@ class _Conv:
                                                  _lib.ptr(self.w_band), _lib.stream_ptr(device)), lib)
         return self.w_band
 
-    def band(self, x, skip=None, x2=None, proj=None):
-        """act(conv3x3(x) (+ conv1x1(x2) of `proj`) + bias (+ skip)) on og_conv_band_* (bias = the sum of both folded biases when a
-        projection rides along, see _Residual)."""
-        n, c, h, w = x.shape
-        cout, st = self.w.shape[0], self.stride[0]
-        lib = _lib.load()
-        self.band_pack(x.device, proj)
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
-        if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-            skip = skip.contiguous(memory_format=torch.channels_last)
-        h2 = w2_ = c2 = 0
-        st2 = 1
-        if proj is not None:
-            x2 = x2 if x2.is_contiguous(memory_format=torch.channels_last) else x2.contiguous(memory_format=torch.channels_last)
-            _, c2, h2, w2_ = x2.shape
-            st2 = proj.stride[0]
-        out = torch.empty((n, cout, (h - 1) // st + 1, (w - 1) // st + 1), dtype=x.dtype, device=x.device,
-                          memory_format=torch.channels_last)
-        self.warm_next(lib)
-        _lib.check(_lib.lp(lib, 'og_conv_band', x.dtype)(
-            _lib.ptr(x), _lib.ptr(self.w_band), _lib.ptr(self.b32), _lib.ptr(skip) if skip is not None else None,
-            _lib.ptr(x2) if proj is not None else None, _lib.ptr(out), n, h, w, c, cout, st, int(self.relu), h2, w2_, c2, st2,
-            _lib.stream_ptr(x.device)), lib)
-        return out
-
-    def pointwise_ok(self, x):
-        """This 1x1 layer can run on og_conv1x1_tiled_* for input x (large levels, channel multiples the kernel serves)."""
-        n, c, h, w = x.shape
-        st = self.stride[0]
-        return ((CONV_TILED & 4) and self.fused and tuple(self.w.shape[2:]) == (1, 1) and tuple(self.pad) == (0, 0)
-                and c % 64 == 0 and self.w.shape[0] % 128 == 0 and x.is_cuda
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and n * ((h - 1) // st + 1) * ((w - 1) // st + 1) >= CONV_PW_MIN_PIXELS)
-
-    def pointwise(self, x, x2=None, other=None, bias=True, skip=None):
-        """act(W x (+ W_other x2) + bias (+ skip)) in one launch; `other` = the second 1x1 layer of the junction (its weight is
-        concatenated along K on first use, its bias is already summed into this layer's).  bias=False / relu off = raw conv."""
-        n, c, h, w = x.shape
-        st, cout = self.stride[0], self.w.shape[0]
-        ho, wo = (h - 1) // st + 1, (w - 1) // st + 1
-        lib = _lib.load()
-        if self.w_tiled is None:
-            assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
-            wcat = self.w.reshape(cout, -1) if other is None else torch.cat([self.w.reshape(cout, -1), other.w.reshape(cout, -1)], 1)
-            wcat = wcat.contiguous()
-            self.w_tiled = torch.empty(wcat.numel(), dtype=self.w.dtype, device=self.w.device)
-            _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(wcat), wcat.shape[1], cout, 2, _lib.ptr(self.w_tiled), _lib.stream_ptr(x.device)), lib)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        if x2 is not None:
-            if x2.shape != x.shape:
-                raise ValueError(f'pointwise: the second input {tuple(x2.shape)} must have the shape of the first {tuple(x.shape)}')
-            if not x2.is_contiguous(memory_format=torch.channels_last):
-                x2 = x2.contiguous(memory_format=torch.channels_last)
-        if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-            skip = skip.contiguous(memory_format=torch.channels_last)
-        out = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        _lib.check(_lib.lp(lib, 'og_conv1x1_tiled', x.dtype)(
-            _lib.ptr(x), c, h, w, st, _lib.ptr(x2) if x2 is not None else None, c if x2 is not None else 0, h, w, st,
-            _lib.ptr(self.w_tiled), _lib.ptr(self.b32) if bias else None, _lib.ptr(skip) if skip is not None else None, _lib.ptr(out),
-            n, ho, wo, cout, int(self.relu and bias), _lib.stream_ptr(x.device)), lib)
-        return out
-
-    def _tiled_s2(self, x, skip):
-        """3x3 stride 2 on og_conv3x3s2_tiled_* (the large down-sampling layers: 320 -> 160, 160 -> 80), epilogue fused."""
-        n, c, h, w = x.shape
-        cout = self.w.shape[0]
-        lib = _lib.load()
-        if self.w_tiled is None:
-            assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
-            self.w_tiled = torch.empty(self.w.numel(), dtype=self.w.dtype, device=self.w.device)
-            _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(self.w), c, cout, 1, _lib.ptr(self.w_tiled), _lib.stream_ptr(x.device)), lib)
-        out = torch.empty((n, cout, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        self.warm_next(lib)
-        _lib.check(_lib.lp(lib, 'og_conv3x3s2_tiled', x.dtype)(_lib.ptr(x), _lib.ptr(self.w_tiled), _lib.ptr(self.b32),
-                                                             _lib.ptr(skip) if skip is not None else None, _lib.ptr(out), n, h, w, c,
-                                                             cout, int(self.relu), _lib.stream_ptr(x.device)), lib)
-        return out
-
-    def up2_ok(self, x):
-        """This layer can run as og_conv3x3_tiled_up2_* on x: the merge of the hourglass level above rides on its epilogue."""
-        n, c, h, w = x.shape
-        return (CONV_UP2 and self.hip3x3 and self.stride[0] == 1 and (CONV_TILED & 1) and n * h * w >= CONV_TILED_MIN_PIXELS
-                and self.w.shape[0] % 128 == 0 and not _WHATIF and x.is_cuda
-                and n * h * w * 4 * self.w.shape[0] < 2 ** 30        # the (N, Cout, 2H, 2W) tensor it updates in place
-                and _lib.load().og_conv3x3_tiled_supported(n, h, w, c, self.w.shape[0]))
-
     def warm_next(self, lib):
         """og_conv_next_weights_hint for the launch that follows: the packed weights of the layer after this one, in whichever layout
         that layer has been run with (none yet during the first warm-up pass: its raw weights then)."""
@@ -376,58 +337,88 @@ class _Conv:
         t = nxt.w_band if nxt.w_band is not None else (nxt.w_tiled if nxt.w_tiled is not None else (nxt.w_alt if nxt.w_alt is not None else nxt.w))
         lib.og_conv_next_weights_hint(_lib.ptr(t), t.numel() * t.element_size())
 
-    def up2(self, x, skip, up):
-        """up += nearest_x2(act(conv(x) + bias + skip)) in one launch (up: (N, Cout, 2H, 2W) channels-last, in place)."""
+    def _launch(self, lib, fn, ins, out, ints, need=None):
+        """What every launcher ends with, its packing and layout copies done: allocate `out` (a shape; a tensor is updated in place),
+        fetch the workspace (need: its bytes; None: the kernel takes none), warm the next layer's weights, then
+        fn(*ins, out, *ints[, workspace, bytes], stream) with the tensors of `ins` (None: a null pointer) as pointers.  -> out"""
+        x = ins[0]
+        if not isinstance(out, torch.Tensor):
+            out = torch.empty(tuple(out), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        buf = _conv3x3_workspace(x.device, need) if need else None
+        ws = () if need is None else (_lib.ptr(buf), buf.numel()) if need else (None, 0)
+        self.warm_next(lib)
+        _lib.check(fn(*[_lib.ptr(t) if t is not None else None for t in ins], _lib.ptr(out), *ints, *ws, _lib.stream_ptr(x.device)), lib)
+        return out
+
+    def band(self, x, skip=None, x2=None, proj=None):
+        """act(conv3x3(x) (+ conv1x1(x2) of `proj`) + bias (+ skip)) on og_conv_band_* (bias = the sum of both folded biases when a
+        projection rides along, see _Residual)."""
+        n, c, h, w = x.shape
+        lib = _lib.load()
+        self.band_pack(x.device, proj)
+        x, skip, x2 = _cl(x), _cl(skip), _cl(x2) if proj is not None else None
+        _, c2, h2, w2 = x2.shape if proj is not None else (0, 0, 0, 0)
+        return self._launch(lib, _lib.lp(lib, 'og_conv_band', x.dtype), (x, self.w_band, self.b32, skip, x2), self.out_shape(x.shape),
+                            (n, h, w, c, self.w.shape[0], self.stride[0], int(self.relu), h2, w2, c2, proj.stride[0] if proj is not None else 1))
+
+    def _tiled(self, x, skip):
+        """3x3 stride 1 on og_conv3x3_tiled_*; the 40- and 20-wide levels split K: tickets + fp32 slabs in the workspace."""
         n, c, h, w = x.shape
         cout = self.w.shape[0]
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        if tuple(up.shape) != (n, cout, 2 * h, 2 * w) or not up.is_contiguous(memory_format=torch.channels_last):
-            raise ValueError(f'up2: `up` must be a channels-last {(n, cout, 2 * h, 2 * w)} tensor, got {tuple(up.shape)}')
-        if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-            skip = skip.contiguous(memory_format=torch.channels_last)
         lib = _lib.load()
-        if self.w_tiled is None:
-            assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
-            self.w_tiled = torch.empty(self.w.numel(), dtype=self.w.dtype, device=self.w.device)
-            _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(self.w), c, cout, 0, _lib.ptr(self.w_tiled), _lib.stream_ptr(x.device)), lib)
-        need = lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout)
-        ws = _conv3x3_workspace(x.device, need) if need else None
-        self.warm_next(lib)
-        _lib.check(_lib.lp(lib, 'og_conv3x3_tiled_up2', x.dtype)(_lib.ptr(x), _lib.ptr(self.w_tiled), _lib.ptr(self.b32),
-                                                                 _lib.ptr(skip) if skip is not None else None, _lib.ptr(up), n, h, w,
-                                                                 c, cout, int(self.relu), _lib.ptr(ws) if need else None,
-                                                                 ws.numel() if need else 0, _lib.stream_ptr(x.device)), lib)
+        wt = self._packed(0)
+        x, skip = _cl(x), _cl(skip)
+        return self._launch(lib, _lib.lp(lib, 'og_conv3x3_tiled', x.dtype), (x, wt, self.b32, skip), self.out_shape(x.shape),
+                            (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout))
 
-    def _hip(self, x, skip):
+    def up2(self, x, skip, up):
+        """up += nearest_x2(act(conv(x) + bias + skip)) in one launch (up: (N, Cout, 2H, 2W) channels-last, in place): the merge of
+        the hourglass level above on the tiled kernel's epilogue."""
+        n, c, h, w = x.shape
+        cout = self.w.shape[0]
+        if tuple(up.shape) != (n, cout, 2 * h, 2 * w) or not _is_cl(up):
+            raise ValueError(f'up2: `up` must be a channels-last {(n, cout, 2 * h, 2 * w)} tensor, got {tuple(up.shape)}')
+        lib = _lib.load()
+        wt = self._packed(0)
+        x, skip = _cl(x), _cl(skip)
+        self._launch(lib, _lib.lp(lib, 'og_conv3x3_tiled_up2', x.dtype), (x, wt, self.b32, skip), up,
+                     (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout))
+
+    def _tiled_s2(self, x, skip):
+        """3x3 stride 2 on og_conv3x3s2_tiled_* (the large down-sampling layers: 320 -> 160, 160 -> 80), epilogue fused; x is
+        channels-last (route)."""
+        n, c, h, w = x.shape
+        lib = _lib.load()
+        wt = self._packed(1)
+        return self._launch(lib, _lib.lp(lib, 'og_conv3x3s2_tiled', x.dtype), (x, wt, self.b32, _cl(skip)), self.out_shape(x.shape),
+                            (n, h, w, c, self.w.shape[0], int(self.relu)))
+
+    def _splitk(self, x, skip):
+        """3x3 stride 1 | 2 on the split-K kernel og_conv2d_* (raw channels-last weights, fp32 slabs in the workspace)."""
         n, c, h, w = x.shape
         cout, st = self.w.shape[0], self.stride[0]
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-            skip = skip.contiguous(memory_format=torch.channels_last)
         lib = _lib.load()
-        out = torch.empty((n, cout, (h - 1) // st + 1, (w - 1) // st + 1), dtype=x.dtype, device=x.device,
-                          memory_format=torch.channels_last)
-        if ((CONV_TILED & 1) and st == 1 and n * h * w >= CONV_TILED_MIN_PIXELS
-                and lib.og_conv3x3_tiled_supported(n, h, w, c, cout)):
-            if self.w_tiled is None:     # tiled once, during the warm-up passes (never inside graph capture)
-                assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
-                self.w_tiled = torch.empty(self.w.numel(), dtype=self.w.dtype, device=self.w.device)
-                _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(self.w), c, cout, 0, _lib.ptr(self.w_tiled), _lib.stream_ptr(x.device)), lib)
-            need = lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout)      # K-split levels: tickets + fp32 slabs
-            ws = _conv3x3_workspace(x.device, need) if need else None
-            self.warm_next(lib)
-            _lib.check(_lib.lp(lib, 'og_conv3x3_tiled', x.dtype)(_lib.ptr(x), _lib.ptr(self.w_tiled), _lib.ptr(self.b32),
-                                                               _lib.ptr(skip) if skip is not None else None, _lib.ptr(out), n, h, w,
-                                                               c, cout, int(self.relu), _lib.ptr(ws) if need else None,
-                                                               ws.numel() if need else 0, _lib.stream_ptr(x.device)), lib)
-            return out
-        ws = _conv3x3_workspace(x.device, lib.og_conv2d_workspace_bytes(n, h, w, c, cout, 3, st))
-        self.warm_next(lib)
-        _lib.check(_lib.lp(lib, 'og_conv2d', x.dtype)(_lib.ptr(x), _lib.ptr(self.w), _lib.ptr(self.b32),
-                                      _lib.ptr(skip) if skip is not None else None, _lib.ptr(out), n, h, w, c, cout, 3, st,
-                                      int(self.relu), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)), lib)
+        x, skip = _cl(x), _cl(skip)
+        return self._launch(lib, _lib.lp(lib, 'og_conv2d', x.dtype), (x, self.w, self.b32, skip), self.out_shape(x.shape),
+                            (n, h, w, c, cout, 3, st, int(self.relu)), lib.og_conv2d_workspace_bytes(n, h, w, c, cout, 3, st))
+
+    def pointwise(self, x, x2=None, other=None, bias=True, skip=None):
+        """act(W x (+ W_other x2) + bias (+ skip)) in one launch on og_conv1x1_tiled_*; `other` = the second 1x1 layer of the junction
+        (its weight is concatenated along K on first use, its bias is already summed into this layer's).  bias=False / relu off = raw
+        conv."""
+        n, c, h, w = x.shape
+        _, cout, ho, wo = self.out_shape(x.shape)
+        st = self.stride[0]
+        lib = _lib.load()
+        wt = self._packed(2, other)
+        if x2 is not None and x2.shape != x.shape:
+            raise ValueError(f'pointwise: the second input {tuple(x2.shape)} must have the shape of the first {tuple(x.shape)}')
+        x, x2, skip = _cl(x), _cl(x2), _cl(skip)
+        out = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        _lib.check(_lib.lp(lib, 'og_conv1x1_tiled', x.dtype)(
+            _lib.ptr(x), c, h, w, st, _lib.ptr(x2) if x2 is not None else None, c if x2 is not None else 0, h, w, st,
+            _lib.ptr(wt), _lib.ptr(self.b32) if bias else None, _lib.ptr(skip) if skip is not None else None, _lib.ptr(out),
+            n, ho, wo, cout, int(self.relu and bias), _lib.stream_ptr(x.device)), lib)
         return out
 
 
@@ -449,6 +440,16 @@ class _Residual:
                                         self.skip.w.reshape(cout, -1)], 1).contiguous()
                 self.c2.w_alt = self.w_cat
 
+    def route(self, x_shape, y_shape, dtype, on_gpu, merge=False, channels_last=True):
+        """-> (shortcut route, conv2 route) of the block on an input of x_shape, conv1's output being y_shape; shapes only.
+        (None, 'band+proj' | 'splitk+proj'): the projection rides along K of conv2, one launch.  Otherwise the shortcut is None (the
+        identity: x itself), 'pointwise' or 'torch' (the raw projection: its bias is in conv2's) and conv2 is routed as a layer
+        (_Conv.route), the merge offered to it.  channels_last: x (y is the output of a convolution: always)."""
+        how = self.c2.route(y_shape, dtype, on_gpu, x2_shape=x_shape, proj=self.skip, merge=merge)
+        if self.skip is None or how.endswith('+proj'):
+            return None, how
+        return 'pointwise' if self.skip.pointwise_ok(x_shape, on_gpu, channels_last) else 'torch', how
+
     def __call__(self, x, merge_up=None, after_c1=None):
         """-> the block's output; with `merge_up` (the up1 tensor of the hourglass level above, channels-last) and conv2 on
         the tiled kernel: merge_up += nearest_x2(output) in conv2's epilogue, returns None (the output is never written).
@@ -456,35 +457,32 @@ class _Residual:
         y = self.c1(x)
         if after_c1 is not None:
             after_c1()
-        n, c, h, w = y.shape
-        if self.skip is not None and self.c2.band_ok(y, x2=x, proj=self.skip):
-            return self.c2.band(y, x2=x, proj=self.skip)      # the projection rides along K; its bias is in c2's
-        if self.w_cat is not None and n * h * w <= CONV3X3_MAX_PIXELS and not _WHATIF:
+        short, how = self.route(tuple(x.shape), tuple(y.shape), y.dtype, y.is_cuda, merge_up is not None, _is_cl(x))
+        if how == 'band+proj':
+            return self.c2.band(y, x2=x, proj=self.skip)
+        if how == 'splitk+proj':
             return self._proj(y, x)
-        if self.skip is None:
-            shortcut = x
-        elif self.skip.pointwise_ok(x) and not _WHATIF:
-            shortcut = self.skip.pointwise(x, bias=False)      # raw projection: its bias rides on conv2's epilogue
-        else:
-            shortcut = self.skip.raw(x)
-        if merge_up is not None and self.c2.up2_ok(y):
+        shortcut = x if short is None else self.skip.pointwise(x, bias=False) if short == 'pointwise' else self.skip.raw(x)
+        if how == 'up2':
             self.c2.up2(y, shortcut, merge_up)
             return None
-        return self.c2(y, skip=shortcut)
+        return self.c2(y, skip=shortcut)      # routed again without the merge: the same answer
 
     def _proj(self, y, x):
+        """relu(conv3x3(y) + conv1x1(x) + bias) on og_conv2d_proj_*: conv2 and the projection as one split-K launch over w_cat."""
         n, c, h, w = y.shape
         _, c2, h2, w2 = x.shape
-        cout, st2 = self.c2.w.shape[0], self.skip.stride[0]
-        assert y.is_contiguous(memory_format=torch.channels_last) and x.is_contiguous(memory_format=torch.channels_last)
+        cout = self.c2.w.shape[0]
+        assert _is_cl(y) and _is_cl(x)
         lib = _lib.load()
-        out = torch.empty((n, cout, h, w), dtype=y.dtype, device=y.device, memory_format=torch.channels_last)
-        ws = _conv3x3_workspace(y.device, lib.og_conv2d_proj_workspace_bytes(n, h, w, c, cout, 3, 1, c2))
-        self.c2.warm_next(lib)
-        _lib.check(_lib.lp(lib, 'og_conv2d_proj', y.dtype)(_lib.ptr(y), _lib.ptr(self.w_cat), _lib.ptr(self.c2.b32), _lib.ptr(x), _lib.ptr(out),
-                                           n, h, w, c, cout, 3, 1, h2, w2, c2, st2, 1, _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr(y.device)), lib)
-        return out
+        return self.c2._launch(lib, _lib.lp(lib, 'og_conv2d_proj', y.dtype), (y, self.w_cat, self.c2.b32, x), (n, cout, h, w),
+                               (n, h, w, c, cout, 3, 1, h2, w2, c2, self.skip.stride[0], 1),
+                               lib.og_conv2d_proj_workspace_bytes(n, h, w, c, cout, 3, 1, c2))
+
+
+def _heads_tiled_ok(cin, heads, channels_last=True):
+    """All heads as one launch of og_conv1x1_heads_* (at most four, on channels-last features of cin channels)."""
+    return bool((CONV_TILED & 4) and cin % 64 == 0 and heads <= 4 and channels_last)
 
 
 def _seq(mods, dtype, fused):
@@ -541,7 +539,7 @@ class _Level:
             side = self._side.get(key)
             if side is None:
                 if DEEP_SHARED and self.depth >= DEEP_SHARED:
-                    if getattr(_issuer, 'deep_side', None) is None or _issuer.deep_side[0] != key:
+                    if _issuer.deep_side is None or _issuer.deep_side[0] != key:
                         _issuer.deep_side = (key, _lib.new_stream(x.device))
                     side = _issuer.deep_side[1]
                 else:
@@ -590,7 +588,7 @@ class _Level:
         else:
             low = self._lower(x)
             up = _run(self.up1, x)
-        low = self.low3[-1](low, merge_up=up if self.fused and up.is_contiguous(memory_format=torch.channels_last) else None)
+        low = self.low3[-1](low, merge_up=up if self.fused and _is_cl(up) else None)
         if low is None:
             return up   # up += nearest_x2(low3(low)) happened in the last convolution's epilogue
         if self.fused:  # up += nearest_x2(low) in one pass
@@ -609,14 +607,17 @@ class _Layers:
               'head_channels')
 
     def __init__(self, model, dtype, device, stage, fused):
-        dev_model = model
         self.heads_b, self.head_channels = None, None
-        net = model.basenet
         self.stage = stage
         # the caller's module is only read: weights are folded from it onto the engine's device (no .to(), no .eval())
         _issuer.build_device = device
         _issuer.names = {id(m): n for n, m in model.named_modules()}
-        dev_model = model
+        try:
+            self._build(model, model.basenet, dtype, fused)
+        finally:      # also when a layer cannot be folded or packed: the next engine built on this thread starts clean
+            _issuer.build_device = _issuer.names = None
+
+    def _build(self, model, net, dtype, fused):
         self.pre = [_Conv(net.pre[0].conv, net.pre[0].bn, True, dtype, fused), _Residual(net.pre[1], dtype, fused)]
         self.kps = [_Level(net.kps[s], dtype, fused) for s in range(self.stage + 1)]
         self.cnvs = [_Conv(net.cnvs[s].conv, net.cnvs[s].bn, True, dtype, fused) for s in range(self.stage + 1)]
@@ -626,7 +627,7 @@ class _Layers:
         for a_, b_ in zip(self.inters_, self.cnvs_):  # relu(inters_(inter) + cnvs_(feat)): one epilogue, summed biases
             a_.b32 = (a_.b32 + b_.b32).contiguous()
             a_.b = a_.b32.to(dtype)
-        hm_head, off_head = dev_model.headnets[0], dev_model.headnets[1]
+        hm_head, off_head = model.headnets[0], model.headnets[1]
         self.hm = _Conv(hm_head.hp_convs[self.stage], None, False, dtype, False)
         self.off = _Conv(off_head.reg_convs[self.stage], None, False, dtype, False)
         # optional keypoint-scale head (models/heads.py:112,136): third element of the offset head's output
@@ -658,8 +659,6 @@ class _Layers:
                 b = torch.cat([b, torch.zeros(pad, dtype=b.dtype, device=b.device)], 0)
             self.heads_w = w.contiguous(memory_format=torch.channels_last)
             self.heads_b = b.contiguous()
-        _issuer.build_device = None
-        _issuer.names = None
 
 
 _layer_cache = {}       # key -> (weak reference to the module, _Layers); at most _LAYER_CACHE_MAX entries, oldest dropped first
@@ -698,7 +697,6 @@ def invalidate_engine_cache():
 
 
 def _shared_layers(model, dtype, device, stage, fused):
-    import weakref
     key = (id(model), _model_signature(model), dtype, str(device), stage, fused)
     hit = _layer_cache.pop(key, None)
     if hit is not None and hit[0]() is not model:     # the id of a module that no longer exists
@@ -748,7 +746,6 @@ class InferenceEngine:
             self._layers = like._layers
         else:
             self._layers = _shared_layers(model, dtype, self.device, self.stage, self.fused)
-        import weakref
         self._model = weakref.ref(model)
         for name in _Layers.FIELDS:
             setattr(self, name, getattr(self._layers, name))
@@ -789,13 +786,12 @@ class InferenceEngine:
         for s in range(self.stage + 1):
             feat = self.cnvs[s](self.kps[s](inter))
             if s < self.stage:
-                if self.inters_[s].pointwise_ok(inter) and feat.shape == inter.shape and not _WHATIF:
+                if self.inters_[s].pointwise_ok(tuple(inter.shape), inter.is_cuda, _is_cl(inter), x2_shape=tuple(feat.shape)):
                     # relu(inters_(inter) + cnvs_(feat)) as ONE 1x1 convolution over the concatenated channels
                     inter = _run([self.inters[s]], self.inters_[s].pointwise(inter, x2=feat, other=self.cnvs_[s]))
                 else:
                     inter = _run([self.inters[s]], self.inters_[s](inter, skip=self.cnvs_[s].raw(feat)))
-        if (self.heads_w is not None and (CONV_TILED & 4) and feat.shape[1] % 64 == 0 and len(self.head_channels) <= 4
-                and feat.is_contiguous(memory_format=torch.channels_last)):
+        if self.heads_w is not None and _heads_tiled_ok(feat.shape[1], len(self.head_channels), _is_cl(feat)):
             lib = _lib.load()
             n, c, h, w = feat.shape
             if self._layers.heads_tiled is None:
@@ -810,7 +806,6 @@ class InferenceEngine:
                 self._layers.heads_tiled = (packed, bpad, cout)
             packed, bpad, cout = self._layers.heads_tiled
             outs = [torch.empty((n, ch, h, w), dtype=torch.float32, device=feat.device) for ch in self.head_channels]
-            import ctypes as C
             chans = (C.c_int * len(outs))(*self.head_channels)
             ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
             _lib.check(_lib.lp(lib, 'og_conv1x1_heads', feat.dtype)(_lib.ptr(feat), c, _lib.ptr(packed), _lib.ptr(bpad), n, h, w, cout,
