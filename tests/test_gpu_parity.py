@@ -89,6 +89,7 @@ def test_topk_channel_exact(dev, shape, k):
 @pytest.mark.parametrize("shape", NMS_SHAPES)
 @pytest.mark.parametrize("k", [1, 32, 48, 200])
 def test_joint_dets_exact(dev, shape, k):
+    # (each geometry once, behind another one: the COLD kernel -- the warm one is pinned in test_gpu_nms_topk_warm.py)
     z = synth.noise_batch(25, shape)
     if k > 2 * (shape[2] + shape[3]) - 4:
         pytest.skip("plane border smaller than k")
