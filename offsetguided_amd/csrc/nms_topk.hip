@@ -63,29 +63,17 @@ __device__ long long g_wave_stamps[2048 * 16];   // band_topk_kernel: [workgroup
 
 namespace {
 
-#ifndef OG_K1_LOAD_AUX
-#define OG_K1_LOAD_AUX 0  // default cache policy.  nt (2) reads an HBM-cold batch 2 us faster (56 vs 58 us for the two launches), but in the
-                          // decode pipeline the batch has just been written by K1a and sits in the Infinity Cache: there nt loads cost
-                          // 60 us (66 behind the backbone) against 57 -- tools/k1_bench.py, every policy (sc0, sc1, nt, combinations)
-#endif
-#ifndef OG_K1_BAND_PF
-#define OG_K1_BAND_PF 3
-#endif
-constexpr int kPrefetch = OG_K1_BAND_PF;      // rows in flight per lane: 3 (2 .. 3 measured best on MI355X: 56.7 us for the three launches, 4: 60.4,
-                                              // 6 / 8: 63.2, 1: 68; deeper queues lose -- more DRAM rows open at once, not occupancy)
-#ifndef OG_K1_BAND_ABL
-#define OG_K1_BAND_ABL 0
-#endif
-constexpr int kBandAbl = OG_K1_BAND_ABL;   // tuning harness, see band_topk_kernel
+constexpr int kLoadAux = 0;  // default cache policy.  nt (2) reads an HBM-cold batch 2 us faster (56 vs 58 us for the two launches), but in the
+                             // decode pipeline the batch has just been written by K1a and sits in the Infinity Cache: there nt loads cost
+                             // 60 us (66 behind the backbone) against 57 -- tools/k1_bench.py, every policy (sc0, sc1, nt, combinations)
+constexpr int kPrefetch = 3;      // rows in flight per lane: 3 (2 .. 3 measured best on MI355X: 56.7 us for the three launches, 4: 60.4,
+                                  // 6 / 8: 63.2, 1: 68; deeper queues lose -- more DRAM rows open at once, not occupancy)
 constexpr int kInterior = 62;     // interior lanes per wave panel
 constexpr int kMaxWaves = 16;     // waves per workgroup (panels per row)
 constexpr uint32_t kLaneOob = 0x80000000u;  // offset of lanes outside the image
 constexpr uint32_t kRowOob = 0x40000000u;   // offset of rows the band must not read
 constexpr int kHistBins = 256;              // per-plane score histogram (NMS mode)
-#ifndef OG_K1_HIST_MBITS
-#define OG_K1_HIST_MBITS 3
-#endif
-constexpr int kHistMBits = OG_K1_HIST_MBITS;                       // bin = exponent + top kHistMBits mantissa bits
+constexpr int kHistMBits = 3;                                      // bin = exponent + top kHistMBits mantissa bits
 constexpr int kHistShift = 23 - kHistMBits;
 constexpr int kHistBase = (127 + 2 - (kHistBins >> kHistMBits)) << kHistMBits;   // the bins end at 2^2; 3 bits: bin 0 starts at 2^-30,
                                                                                   // 4 bits: 2^-14 (everything smaller joins bin 0)
@@ -161,7 +149,7 @@ __device__ __forceinline__ void walk_panel(const float *plane, const TileGeom &g
         Px<VEC> r;
         if constexpr (VEC == 4) {
             typedef float v4f __attribute__((ext_vector_type(4)));
-            const v4f t = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, OG_K1_LOAD_AUX));
+            const v4f t = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, kLoadAux));
             r.c[0] = t.x; r.c[1] = t.y; r.c[2] = t.z; r.c[3] = t.w;
         } else {
             r.c[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
@@ -309,35 +297,17 @@ __device__ __forceinline__ void walk_panel_fused(const float *__restrict__ lr, c
     }
 }
 
-// Work items of the band kernel: plane p is cut into b_lo or b_lo + 1 bands (n_hi of the planes, spread evenly, take the extra
-// one), so that the launch has a chosen number of workgroups -- a multiple of the CU count: at bs8 640x640 1 024 instead of
-// 136 x 8 = 1 088, whose 64 extra workgroups put a fifth one on every fourth CU and set the end of the stream (stamps:
-// 36 us against 32.5 us for the others).  Item index = start(p) + band; band boundaries are multiples of 4 rows.
-struct BandMap {
-    int planes, b_lo, n_hi;
-};
-// (32-bit arithmetic: make_plan only builds maps whose products fit -- 64-bit divisions cost the band kernel 1 us of set-up)
-__host__ __device__ __forceinline__ int bm_start(const BandMap &m, int p) { return p * m.b_lo + (int)(((unsigned)p * (unsigned)m.n_hi) / (unsigned)m.planes); }
+// Work items of the band kernel: every plane is cut into the same `nbands` bands, item index = plane * nbands + band; band
+// boundaries are multiples of 4 rows.  (History: a balanced map -- some planes one band more, so that the launch is a multiple of
+// the CU count: at bs8 640x640 1 024 workgroups instead of 136 x 8 = 1 088, whose 64 extra ones put a fifth workgroup on every
+// fourth CU and set the end of the stream, stamps: 36 us against 32.5 us for the others -- was built and lost in the decode
+// pipeline: EXPERIMENTS.md.)
+// (32-bit arithmetic: 64-bit divisions cost the band kernel 1 us of set-up)
 __host__ __device__ __forceinline__ int bm_row(int b, int nb, int H)
 {
     if (b >= nb) return H;
     if (H < (1 << 20)) return (int)((((unsigned)b * (unsigned)H) / (unsigned)nb) & ~3u);   // (at most 64 bands)
     return (int)((((long)b * H) / nb) & ~3l);
-}
-__device__ __forceinline__ void bm_locate(const BandMap &m, int total, int wid, int &plane, int &band, int &nb)
-{
-    if (m.n_hi == 0) {   // equal band counts (any number of planes)
-        plane = wid / m.b_lo;
-        band = wid - plane * m.b_lo;
-        nb = m.b_lo;
-        return;
-    }
-    int p = (int)(((unsigned)wid * (unsigned)m.planes) / (unsigned)total);
-    while (p + 1 < m.planes && bm_start(m, p + 1) <= wid) ++p;
-    while (p > 0 && bm_start(m, p) > wid) --p;
-    plane = p;
-    band = wid - bm_start(m, p);
-    nb = bm_start(m, p + 1) - bm_start(m, p);
 }
 
 __device__ __forceinline__ TileGeom make_geom(int H, int W, int r0, int r1, int panel_strips, int vec)
@@ -404,7 +374,7 @@ struct WaveSeg {
     int lane_tau_bits;
     float lane_tau_f;
     int *hist;            // plane histogram (global) or nullptr
-    int npush = 0;        // debug statistics (OG_K1_DEBUG)
+    int npush = 0;        // candidates pushed / compactions run: read only by the stamps build (OG_K1_STAMPS, WAVE_STAMP)
     int ncompact = 0;
 
     __device__ __forceinline__ void set_tau(float t)
@@ -471,10 +441,6 @@ struct WaveSeg {
     }
 };
 
-// ABL (tuning harness only, -DOG_K1_BAND_ABL): 0 = product; 1 = compute the admission masks but never push; 3 = loads and
-// threshold ballots only; 4 = the whole NMS test (3x3 maxima, peak masks) without the candidate handling.
-// FUSED: `in` holds the stride-4 head output (planes x H/4 x W/4) and the hi-res rows are produced on
-// the fly (walk_panel_fused) instead of being read from a materialised (planes x H x W) tensor.
 // One plane's merge by `nthr` consecutive threads (tid = 0..nthr-1 within the group; every thread of the workgroup calls
 // this the same number of times: it contains workgroup barriers).  gk: the plane's `nlists` sorted lists of k keys each,
 // zero-padded by their writers (a key is never zero).  `all` / `flt`: n_all = nlists * k keys each, in LDS;
@@ -563,12 +529,14 @@ __device__ __forceinline__ void merge_plane(const uint64_t *__restrict__ gk, uin
     }
 }
 
-template <int VEC, bool NMS_MODE, int PF, int ABL = 0, bool FUSED = false>
+// FUSED: `in` holds the stride-4 head output (planes x H/4 x W/4) and the hi-res rows are produced on
+// the fly (walk_panel_fused) instead of being read from a materialised (planes x H x W) tensor.
+template <int VEC, bool NMS_MODE, int PF, bool FUSED = false>
 // (amdgpu_waves_per_eu: <= 96 VGPRs -- at bs8 640x640 all 1 088 workgroups must be resident together, 5 per CU)
 __global__ void __launch_bounds__(64 * kMaxWaves) __attribute__((amdgpu_waves_per_eu(5)))
 band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
                  int *__restrict__ hist_all, uint64_t *__restrict__ ws_magic, uint64_t magic,
-                 int H, int W, int k, int cap, BandMap bm, int max_bands, int panel_strips, int total, int padded, int helper,
+                 int H, int W, int k, int cap, int nbands, int panel_strips, int total, int padded, int helper,
                  int wl, FlipSrc fs)
 {
     // all LDS comes from the dynamic region (no static __shared__ in front of it: the base stays
@@ -582,8 +550,7 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
     BAND_STAMP(0);
     const int wid = og_xcd_remap(blockIdx.x, padded);
     if (wid >= total) return;
-    int plane, band, nbands;   // nbands: bands of THIS plane
-    bm_locate(bm, total, wid, plane, band, nbands);
+    const int plane = wid / nbands, band = wid - plane * nbands;
     const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     TileGeom g = make_geom(H, W, bm_row(band, nbands, H), bm_row(band + 1, nbands, H), panel_strips, VEC);
     int q_lane = 0;
@@ -604,7 +571,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
     seg.emits = g.interior;  // (VEC == 1: every interior lane is inside the image as well)
     if (NMS_MODE) seg.set_tau(__builtin_bit_cast(float, 1));  // bits >= 1  <=>  v > +0
     else seg.set_tau(-INFINITY);
-    if (ABL == 2) seg.set_tau(0.035f);  // harness: what a perfect plane-wide threshold would buy
     // Plane-wide admission threshold, no atomics on global memory and NO vector-memory operation in
     // the streaming waves' loop (any conditional one makes the compiler drain the row prefetch queue
     // with vmcnt(0) every iteration -- ~5 us each under load).  The streaming waves only ds_add their
@@ -616,8 +582,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
     //   k-th best (4 bands x t >= k candidates above it) -> s_tau = max(...) in LDS -> sleep.
     // Slots only grow and every bound is a true lower bound whatever the timing, so the top-k stays
     // exact.  The table is trusted only if the workspace carries this geometry's magic word.
-    const int hmode = helper;   // bit 0: helper wave present; bit 3: debug statistics (tools/)
-    helper &= 1;
     const int nstream = (blockDim.x >> 6) - helper;   // streaming waves
     // The workspace check (one memory round trip) and the LDS set-up behind it run AFTER a streaming wave has issued the
     // loads of its first rows (walk_panel's `mid`): the stream starts one round trip earlier.  Every wave passes through
@@ -626,7 +590,7 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
     seg.hist = nullptr;
     int *s_done = s_tau_p + 1;
     auto setup = [&](int) {
-        gslot = (NMS_MODE && helper && *ws_magic == magic) ? hist_all + (size_t)plane * max_bands : nullptr;
+        gslot = (NMS_MODE && helper && *ws_magic == magic) ? hist_all + (size_t)plane * nbands : nullptr;
         seg.hist = gslot ? s_hist : nullptr;
         if (gslot) {
             for (int i = threadIdx.x; i < kHistBins; i += blockDim.x) s_hist[i] = 0;
@@ -736,11 +700,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
                                                          : (v.c[j] >= seg.lane_tau_f));
             any |= ge[j];
         }
-        if (ABL == 1) {
-            seg.cnt += (int)(any >> 63);  // keep the masks alive
-            return;
-        }
-        if (ABL == 3) return;   // harness: loads + threshold ballots only (the access pattern's own ceiling)
         if (any != 0ull) {
             Px<VEC> m;
             if (NMS_MODE) m = vmax3<VEC>(ha, hb, hc);
@@ -753,10 +712,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
             for (int j = 0; j < VEC; ++j) {
                 mj[j] = NMS_MODE ? (ge[j] & __builtin_amdgcn_ballot_w64(v.c[j] == m.c[j])) : ge[j];
                 many |= mj[j];
-            }
-            if (ABL == 4) {   // harness: the whole NMS test, no candidate handling
-                seg.cnt += (int)(many >> 63);
-                return;
             }
             if (many != 0ull) {
 #pragma unroll
@@ -777,10 +732,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
         }
     }
     if (gslot && lane_id == 0 && wave < nstream && !reported) atomicAdd(s_done, 1);
-    if ((hmode & 8) && hist_all && lane_id == 0 && wave < nstream) {  // debug: pushes / final threshold / waves, kept in the unused tail of the slot region
-        int *dbg = hist_all + (size_t)bm.planes * kHistBins - 16;
-        atomicAdd(dbg + 0, seg.npush); atomicMax(dbg + 1, seg.tau_bits); atomicAdd(dbg + 2, 1); atomicAdd(dbg + 3, seg.tau_bits > 1 ? 1 : 0);
-    }
 
     BAND_STAMP(2);
     WAVE_STAMP(0, wall_clock64());
@@ -821,13 +772,6 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
 }
 
 // ---------------------------------------------------------------------------------------
-// merge kernel: one wave per plane selects the plane's top-k from the sorted band lists.
-//   A) a lower bound L on the k-th best: the k-th largest among the first `t` keys of every
-//      band (a subset of all keys, so the true k-th best is >= L);
-//   B) compact the keys >= L (usually just over k of them);
-//   C) rank them by counting and write the k best in order.
-// ---------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------
 // merge kernel: one workgroup per plane selects the plane's top-k from the sorted band lists.
 //   A) a lower bound L on the k-th best: the k-th largest among the first `t` keys of every
 //      band (a subset of all keys, so the true k-th best is >= L);
@@ -837,20 +781,20 @@ band_topk_kernel(const float *__restrict__ in, uint64_t *__restrict__ band_keys,
 template <bool NMS_MODE, bool FUSED = false>
 __global__ void __launch_bounds__(256)
 merge_bands_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all, uint64_t *__restrict__ ws_magic,
-                   uint64_t magic, const float *__restrict__ in, int H, int W, int k, BandMap bm, int max_bands, int wl, int t_sub,
+                   uint64_t magic, const float *__restrict__ in, int H, int W, int k, int nbands, int wl, int t_sub,
                    float *__restrict__ out_scores, int64_t *__restrict__ out_inds, FlipSrc fs)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     const int plane = blockIdx.x, tid = threadIdx.x;
-    const int first = bm_start(bm, plane), nlists = (bm_start(bm, plane + 1) - first) * wl;
+    const int first = plane * nbands, nlists = nbands * wl;
     __shared__ uint64_t s_bound;
     __shared__ int s_nf;
     float *os = out_scores + (size_t)plane * k;
     int64_t *oi = out_inds + (size_t)plane * k;
     if (hist_all)  // leave the workspace clean (zero slots + this geometry's magic) for the next call
-        for (int i = tid; i < max_bands; i += blockDim.x) hist_all[(size_t)blockIdx.x * max_bands + i] = 0;
+        for (int i = tid; i < nbands; i += blockDim.x) hist_all[(size_t)blockIdx.x * nbands + i] = 0;
     if (blockIdx.x == 0 && tid == 0) *ws_magic = hist_all ? magic : 0ull;
-    merge_plane<NMS_MODE, FUSED>(band_keys + (size_t)first * wl * k, lds64, lds64 + (size_t)max_bands * wl * k,
+    merge_plane<NMS_MODE, FUSED>(band_keys + (size_t)first * wl * k, lds64, lds64 + (size_t)nlists * k,
                                  &s_bound, &s_nf, tid, 256,
                                  in + (FUSED ? (size_t)plane * (H >> 2) * (W >> 2) : (size_t)plane * H * W), H, W, k, nlists,
                                  t_sub, [&](int rank, float v, long idx) { os[rank] = v; oi[rank] = (int64_t)idx; },
@@ -863,17 +807,16 @@ merge_bands_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ his
 // workspace.  A plane is merged by every limb that uses it (2.2 times on the COCO skeleton): 4 KB of L2 reads each, against
 // a launch, a launch gap and a round trip of the lists through memory.
 // FUSED: `in` = the stride-4 heat maps (the zero-fill path of merge_plane evaluates the x4 bicubic at single points).
-// The body is shared by merge_collect_kernel (the pairing of og_collect::Args, unchanged) and merge_collect_scored_kernel (ArgsT =
-// og_collect::ScoredArgs: scored_off, the offset taps refined on the spot); lds64 / s_bound / s_nf are the kernel's LDS.
+// lds64 / s_bound / s_nf are the kernel's LDS.
 template <int ND, bool FUSED, class ArgsT>
 __device__ __forceinline__ void
 merge_collect_body(uint64_t *lds64, uint64_t *s_bound, int *s_nf, const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
-                   uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, const BandMap &bm, int max_bands,
+                   uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, int planes, int nbands,
                    int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, const ArgsT &a, int NL,
                    const FlipSrc &fs)
 {
     MERGE_STAMP(0);
-    const int planes = bm.planes, k = a.K, H = a.H, W = a.W, n_all = max_bands * wl * k, Kp = (k + 3) & ~3;   // n_all: LDS carve-up
+    const int k = a.K, H = a.H, W = a.W, n_all = nbands * wl * k, Kp = (k + 3) & ~3;   // n_all: LDS carve-up
     const int half = threadIdx.x >> 8, tid = threadIdx.x & 255;
     uint64_t *all = lds64 + (size_t)half * 2 * n_all, *flt = all + n_all;
     float *ls = reinterpret_cast<float *>(lds64 + 4 * (size_t)n_all);   // [2][Kp] scores | [2][Kp] indices | pairing scratch
@@ -891,13 +834,13 @@ merge_collect_body(uint64_t *lds64, uint64_t *s_bound, int *s_nf, const uint64_t
         live = plane < planes;
         plane = live ? plane : planes - 1;   // the odd plane out: merged twice, written once
         if (live && hist_all)
-            for (int i = tid; i < max_bands; i += 256) hist_all[(size_t)plane * max_bands + i] = 0;
+            for (int i = tid; i < nbands; i += 256) hist_all[(size_t)plane * nbands + i] = 0;
         if (plane == 0 && tid == 0) *ws_magic = hist_all ? magic : 0ull;
     }
     float *os = limb ? ls + half * Kp : out_scores + (size_t)plane * k;
     int *oi32 = li + half * Kp;
     int64_t *oi64 = out_inds + (size_t)plane * k;
-    const int first = bm_start(bm, plane), nlists = (bm_start(bm, plane + 1) - first) * wl;
+    const int first = plane * nbands, nlists = nbands * wl;
     const size_t plane_elems = FUSED ? (size_t)(H >> 2) * (W >> 2) : (size_t)H * W;
     merge_plane<true, FUSED>(band_keys + (size_t)first * wl * k, all, flt, &s_bound[half],
                              &s_nf[half], tid, 256, in + (size_t)plane * plane_elems, H, W, k, nlists, t_sub,
@@ -913,56 +856,25 @@ merge_collect_body(uint64_t *lds64, uint64_t *s_bound, int *s_nf, const uint64_t
     MERGE_STAMP(2);
 }
 
-template <int ND, bool FUSED = false>
+// ArgsT selects the pairing, one instantiation each with its own registers and LDS: og_collect::Args (ND = 2 or 4), ScoredArgs
+// (scored_off: 2-component offsets, their taps refined on the spot from the stride-4 heat maps), or FlipHeadsArgs<either> (flip-test
+// with the scale / jitter heads sampled from the [images | mirrored images] pairs; K1-fused only).
+template <int ND, bool FUSED, class ArgsT>
 __global__ void __launch_bounds__(512)
 merge_collect_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
-                     uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
-                     int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, og_collect::Args a, int NL,
+                     uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, int planes, int nbands,
+                     int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds, ArgsT a, int NL,
                      FlipSrc fs)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     __shared__ uint64_t s_bound[2];
     __shared__ int s_nf[2];
-    merge_collect_body<ND, FUSED>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
+    merge_collect_body<ND, FUSED>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, planes, nbands, wl, t_sub, out_scores,
                                   out_inds, a, NL, fs);
 }
 
-// scored_off: the same launch with the refined offset sampling (2-component offsets sampled from the stride-4 map)
-template <bool FUSED>
-__global__ void __launch_bounds__(512)
-merge_collect_scored_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
-                            uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
-                            int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds,
-                            og_collect::ScoredArgs a, int NL, FlipSrc fs)
-{
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
-    __shared__ uint64_t s_bound[2];
-    __shared__ int s_nf[2];
-    merge_collect_body<2, FUSED>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
-                                 out_inds, a, NL, fs);
-}
-
-// flip-test with the scale / jitter heads sampled from the [images | mirrored images] pairs (og_collect::FlipHeadsArgs): instantiated
-// apart from the two kernels above, which keep their registers and LDS; K1-fused only.
-template <bool SCORED>
-__global__ void __launch_bounds__(512)
-merge_collect_heads_kernel(const uint64_t *__restrict__ band_keys, int *__restrict__ hist_all,
-                           uint64_t *__restrict__ ws_magic, uint64_t magic, const float *__restrict__ in, BandMap bm, int max_bands,
-                           int wl, int t_sub, float *__restrict__ out_scores, int64_t *__restrict__ out_inds,
-                           og_collect::FlipHeadsArgs<std::conditional_t<SCORED, og_collect::ScoredArgs, og_collect::Args>> a, int NL,
-                           FlipSrc fs)
-{
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
-    __shared__ uint64_t s_bound[2];
-    __shared__ int s_nf[2];
-    merge_collect_body<2, true>(lds64, s_bound, s_nf, band_keys, hist_all, ws_magic, magic, in, bm, max_bands, wl, t_sub, out_scores,
-                                out_inds, a, NL, fs);
-}
-
 struct Plan {
-    int vec, rows, nbands, panel_strips, nwaves, cap, t_sub;   // rows / nbands: equal bands (og_hmp_nms_f32)
-    BandMap bm;       // the band kernel's work items
-    int max_bands;    // most bands a plane has (slot table stride, LDS of the merge stage)
+    int vec, rows, nbands, panel_strips, nwaves, cap, t_sub;   // nbands bands of `rows` rows (og_hmp_nms_f32; the band kernel: bm_row)
     int total;        // work items = workgroups of the band kernel
     int wl;           // sorted k-lists a band hands to the merge: one (cross-wave ranking in the band kernel) or one per streaming wave
     size_t keys_off, hist_off, magic_off, bytes;
@@ -975,34 +887,36 @@ int env_int(const char *name, int dflt)
     return (s && *s) ? atoi(s) : dflt;
 }
 
-inline int device_cu_count() { return og_cu_count(); }
-
-bool make_plan(long planes, int H, int W, int k, bool aligned16, Plan *p)
+// K1's geometry, decided here alone.  nwaves / panel_strips / wl / t_sub are those of the form that runs (`fused`: lanes are source
+// columns, 58 interior per wave); bytes, the offsets and the magic word are those of the unfused form whatever `fused` says, so that
+// one og_topk_workspace_bytes holds for both.
+bool make_plan(long planes, int H, int W, int k, bool aligned16, bool fused, Plan *p)
 {
     p->vec = (W % 4 == 0 && aligned16) ? 4 : 1;
     const int strips = (W + p->vec - 1) / p->vec;
-    p->nwaves = (strips + kInterior - 1) / kInterior;
-    if (p->nwaves > kMaxWaves) return false;
-    p->panel_strips = (strips + p->nwaves - 1) / p->nwaves;
+    const int ws_waves = (strips + kInterior - 1) / kInterior;   // the unfused form's waves: they size the workspace
+    if (ws_waves > kMaxWaves) return false;
+    const int cols = fused ? W / 4 : strips, interior = fused ? 58 : kInterior;
+    p->nwaves = (cols + interior - 1) / interior;                // (fused: run_topk turns away nwaves >= kMaxWaves)
+    p->panel_strips = (cols + p->nwaves - 1) / p->nwaves;
     int rows = env_int("OG_NMS_ROWS", 80);
     rows = max(rows, (H + 63) / 64);    // the slot table is scanned by one wave: at most 64 bands
     rows = min(rows, H);
     p->rows = rows;
     p->nbands = (H + rows - 1) / rows;
     // Work items: equal bands of OG_NMS_ROWS rows.  (A balanced map -- exactly n workgroups per CU, bands of 85 / 86 rows -- was 1 us
-    // faster stand-alone on HBM-cold data and 0-2 us slower in the decode pipeline: EXPERIMENTS.md; BandMap still describes both.)
-    p->bm = BandMap{(int)planes, p->nbands, 0};
-    p->max_bands = p->bm.b_lo + (p->bm.n_hi > 0 ? 1 : 0);
-    p->total = bm_start(p->bm, (int)planes);
+    // faster stand-alone on HBM-cold data and 0-2 us slower in the decode pipeline: EXPERIMENTS.md.)
+    p->total = (int)planes * p->nbands;
     p->cap = (2 * k + 64 + 63) / 64 * 64;
-    if ((size_t)p->nwaves * 2 * p->cap * sizeof(uint64_t) > 60 * 1024) return false;
+    if ((size_t)ws_waves * 2 * p->cap * sizeof(uint64_t) > 60 * 1024) return false;
     // One list per streaming wave when the merge stage can hold them (4 x lists x k keys of LDS for a limb's two planes):
     // the band kernel then ends without a workgroup barrier and without ranking its waves' lists against each other
     // (3.4 us per workgroup at bs8 640x640, all of it exposed behind the last band); OG_K1_WAVE_LISTS=0: one list per band.
     static const int wave_lists = env_int("OG_K1_WAVE_LISTS", 1);
-    p->wl = (wave_lists && p->nwaves > 1 && (size_t)4 * p->max_bands * p->nwaves * k * sizeof(uint64_t) <= 40 * 1024) ? p->nwaves : 1;
+    const int ws_wl = (wave_lists && ws_waves > 1 && (size_t)4 * p->nbands * ws_waves * k * sizeof(uint64_t) <= 40 * 1024) ? ws_waves : 1;
+    p->wl = p->nwaves == ws_waves ? ws_wl : 1;   // (a fused wave count of its own: the workspace is sized for the other one, one list per band)
     // subset depth for the merge's lower bound: lists * t_sub >= k whenever possible
-    const int min_lists = p->bm.b_lo * p->wl;
+    const int min_lists = p->nbands * p->wl;
     p->t_sub = min(k, max(2, (k + min_lists - 1) / min_lists + 1));
     // [magic | slot tables | band keys]; the magic word sits at offset 0 for every shape and encodes the shape and the
     // work-item map, so a call with another geometry (or in plain top-k mode) invalidates whatever slot-table state an
@@ -1010,7 +924,7 @@ bool make_plan(long planes, int H, int W, int k, bool aligned16, Plan *p)
     p->magic_off = 0;
     p->hist_off = 256;
     p->keys_off = p->hist_off + og_align_up((size_t)planes * kHistBins * sizeof(int), 256);
-    p->bytes = p->keys_off + og_align_up((size_t)p->total * p->wl * k * sizeof(uint64_t), 256);
+    p->bytes = p->keys_off + og_align_up((size_t)p->total * ws_wl * k * sizeof(uint64_t), 256);
     p->magic = kWsMagic ^ ((uint64_t)planes * 0x9E3779B97F4A7C15ull + (uint64_t)H * 0x100000001B3ull +
                            (uint64_t)W * 0xC2B2AE3D27D4EB4Full + (uint64_t)k * 0x165667B19E3779F9ull +
                            (uint64_t)p->total * 0x27D4EB2F165667C5ull);
@@ -1020,7 +934,7 @@ bool make_plan(long planes, int H, int W, int k, bool aligned16, Plan *p)
 struct Pairing {   // og_generate_limbs_f32: the merge launch pairs the limbs as well
     og_collect::Args a;
     int nd, N;
-    const float *score_hm = nullptr;     // scored_off (og_collect::ScoredArgs): score_ks > 0 selects merge_collect_scored_kernel
+    const float *score_hm = nullptr;     // scored_off (og_collect::ScoredArgs): score_ks > 0 selects that instantiation
     int score_ks = 0;
     const int32_t *kp_perm = nullptr;
     // og_collect::FlipHeadsArgs: the flip fold with a scale / jitter pair (K1-fused only, kp_perm set)
@@ -1038,82 +952,71 @@ int run_topk(const float *in, long planes, int H, int W, int k, float *out_score
     OG_REQUIRE((long)H * W < (1l << 27), OG_EINVAL, "%s: plane too large", name);
     if (NMS_MODE) OG_REQUIRE(2l * (H + W) - 4 >= k, OG_EINVAL, "%s: plane border smaller than k", name);
     Plan p;
-    OG_REQUIRE(make_plan(planes, H, W, k, (uintptr_t)in % 16 == 0, &p), OG_EUNSUPPORTED, "%s: unsupported W=%d or k=%d",
+    OG_REQUIRE(make_plan(planes, H, W, k, (uintptr_t)in % 16 == 0, FUSED, &p), OG_EUNSUPPORTED, "%s: unsupported W=%d or k=%d",
                name, W, k);
-    int wl = p.wl, t_sub = p.t_sub;
-    if (FUSED) {  // lanes are source columns (58 interior per wave); bands start on a source row (bm_row: multiples of 4)
-        const int w4 = W / 4;
-        OG_REQUIRE((w4 + 57) / 58 < kMaxWaves, OG_EUNSUPPORTED, "%s: W=%d too wide", name, W);
-        const int plan_waves = p.nwaves;
-        p.nwaves = (w4 + 57) / 58;
-        p.panel_strips = (w4 + p.nwaves - 1) / p.nwaves;
-        if (p.nwaves != plan_waves) {   // (the plan sized the workspace for ITS wave count: one list per band then)
-            wl = 1;
-            t_sub = min(k, max(2, (k + p.bm.b_lo - 1) / p.bm.b_lo + 1));
-        }
-    }
+    OG_REQUIRE(!FUSED || p.nwaves < kMaxWaves, OG_EUNSUPPORTED, "%s: W=%d too wide", name, W);
+    const int wl = p.wl, t_sub = p.t_sub;
     OG_REQUIRE(workspace_bytes >= p.bytes, OG_ENOSPC, "%s: workspace %zu < %zu", name, workspace_bytes, p.bytes);
     OG_REQUIRE((uintptr_t)workspace % 8 == 0, OG_EINVAL, "%s: workspace must be 8-byte aligned", name);
     uint64_t *keys = reinterpret_cast<uint64_t *>((char *)workspace + p.keys_off);
-    int *hist = (NMS_MODE && p.max_bands <= 64) ? reinterpret_cast<int *>((char *)workspace + p.hist_off) : nullptr;
+    int *hist = (NMS_MODE && p.nbands <= 64) ? reinterpret_cast<int *>((char *)workspace + p.hist_off) : nullptr;
     uint64_t *magic = reinterpret_cast<uint64_t *>((char *)workspace + p.magic_off);
 
     const long total = p.total;
     OG_REQUIRE(total < (1l << 30), OG_EINVAL, "%s: too many work items", name);
     const int padded = (int)((total + 7) / 8 * 8);
     const int helper = (hist != nullptr && p.nwaves < kMaxWaves) ? 1 : 0;   // extra wave: threshold exchange
-    const dim3 block(64 * (p.nwaves + (helper & 1)));
-    const size_t lds = (size_t)(p.nwaves + (helper & 1)) * 2 * p.cap * sizeof(uint64_t) + (kHistBins + 2 * kMaxWaves + 4) * sizeof(int);
+    const dim3 block(64 * (p.nwaves + helper));
+    const size_t lds = (size_t)(p.nwaves + helper) * 2 * p.cap * sizeof(uint64_t) + (kHistBins + 2 * kMaxWaves + 4) * sizeof(int);
     if (FUSED)
-        hipLaunchKernelGGL((band_topk_kernel<4, NMS_MODE, kPrefetch, kBandAbl, true>), dim3(padded), block, lds, stream, in, keys,
-                           hist, magic, p.magic, H, W, k, p.cap, p.bm, p.max_bands, p.panel_strips, (int)total, padded,
+        hipLaunchKernelGGL((band_topk_kernel<4, NMS_MODE, kPrefetch, true>), dim3(padded), block, lds, stream, in, keys,
+                           hist, magic, p.magic, H, W, k, p.cap, p.nbands, p.panel_strips, (int)total, padded,
                            helper, wl, fs);
     else if (p.vec == 4)
-        hipLaunchKernelGGL((band_topk_kernel<4, NMS_MODE, kPrefetch, kBandAbl>), dim3(padded), block, lds, stream, in, keys,
-                           hist, magic, p.magic, H, W, k, p.cap, p.bm, p.max_bands, p.panel_strips, (int)total, padded, helper,
+        hipLaunchKernelGGL((band_topk_kernel<4, NMS_MODE, kPrefetch>), dim3(padded), block, lds, stream, in, keys,
+                           hist, magic, p.magic, H, W, k, p.cap, p.nbands, p.panel_strips, (int)total, padded, helper,
                            wl, fs);
     else
         hipLaunchKernelGGL((band_topk_kernel<1, NMS_MODE, kPrefetch>), dim3(padded), block, lds, stream, in, keys,
-                           hist, magic, p.magic, H, W, k, p.cap, p.bm, p.max_bands, p.panel_strips, (int)total, padded, helper,
+                           hist, magic, p.magic, H, W, k, p.cap, p.nbands, p.panel_strips, (int)total, padded, helper,
                            wl, fs);
     OG_LAUNCH_CHECK(name);
     // dynamic LDS the merge kernels may ask for without raising the 64 KiB default: their static __shared__ words (bounds,
     // counters: 24 B) come on top
     constexpr size_t kDynLdsLimit = 64 * 1024 - 256;
-    const size_t mlds = (size_t)2 * p.max_bands * wl * k * sizeof(uint64_t);
+    const size_t mlds = (size_t)2 * p.nbands * wl * k * sizeof(uint64_t);
     OG_REQUIRE(mlds <= kDynLdsLimit, OG_EUNSUPPORTED, "%s: k*bands too large for the merge stage", name);
     if constexpr (NMS_MODE) {
         const size_t plds = 2 * mlds + (size_t)((k + 3) & ~3) * 32;
         if (pair && plds <= kDynLdsLimit) {
             const int NL = pair->N * pair->a.L;
+            const auto launch = [&](auto nd, const auto &a) {
+                hipLaunchKernelGGL((merge_collect_kernel<decltype(nd)::value, FUSED, std::decay_t<decltype(a)>>),
+                                   dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds, stream, keys, hist, magic, p.magic, in,
+                                   (int)planes, p.nbands, wl, t_sub, out_scores, out_inds, a, NL, fs);
+            };
+            const std::integral_constant<int, 2> nd2;
+            const bool scored = pair->score_ks > 0;
             if (FUSED && pair->flip_heads()) {
-                const dim3 grid((unsigned)(NL + (planes + 1) / 2));
-                if (pair->score_ks > 0) {
-                    const og_collect::FlipHeadsArgs<og_collect::ScoredArgs> ha{{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm},
-                                                                               pair->kp_perm};
-                    hipLaunchKernelGGL((merge_collect_heads_kernel<true>), grid, dim3(512), plds, stream, keys, hist, magic, p.magic, in,
-                                       p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, ha, NL, fs);
-                } else {
-                    const og_collect::FlipHeadsArgs<og_collect::Args> ha{pair->a, pair->kp_perm};
-                    hipLaunchKernelGGL((merge_collect_heads_kernel<false>), grid, dim3(512), plds, stream, keys, hist, magic, p.magic, in,
-                                       p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, ha, NL, fs);
+                if constexpr (FUSED) {   // (FlipHeadsArgs is instantiated for K1-fused alone)
+                    if (scored)
+                        launch(nd2, og_collect::FlipHeadsArgs<og_collect::ScoredArgs>{{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm},
+                                                                                      pair->kp_perm});
+                    else launch(nd2, og_collect::FlipHeadsArgs<og_collect::Args>{pair->a, pair->kp_perm});
                 }
-            } else if (pair->score_ks > 0) {
-                const og_collect::ScoredArgs sa{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm};
-                hipLaunchKernelGGL((merge_collect_scored_kernel<FUSED>), dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds,
-                                   stream, keys, hist, magic, p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, sa, NL,
-                                   fs);
+            } else if (scored) {
+                launch(nd2, og_collect::ScoredArgs{pair->a, pair->score_hm, pair->score_ks, pair->kp_perm});
+            } else if (pair->nd == 2) {
+                launch(nd2, pair->a);
             } else {
-                auto kern = pair->nd == 2 ? merge_collect_kernel<2, FUSED> : merge_collect_kernel<4, FUSED>;
-                hipLaunchKernelGGL(kern, dim3((unsigned)(NL + (planes + 1) / 2)), dim3(512), plds, stream, keys, hist, magic,
-                                   p.magic, in, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, pair->a, NL, fs);
+                launch(std::integral_constant<int, 4>(), pair->a);
             }
             OG_LAUNCH_CHECK(name);
             return 1;   // paired
         }
     }
     hipLaunchKernelGGL((merge_bands_kernel<NMS_MODE, FUSED>), dim3((unsigned)planes), dim3(256), mlds, stream, keys, hist,
-                       magic, p.magic, in, H, W, k, p.bm, p.max_bands, wl, t_sub, out_scores, out_inds, fs);
+                       magic, p.magic, in, H, W, k, p.nbands, wl, t_sub, out_scores, out_inds, fs);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }
@@ -1124,7 +1027,7 @@ OG_API size_t og_topk_workspace_bytes(long planes, int H, int W, int k)
 {
     Plan p;
     if (planes <= 0 || H <= 0 || W <= 0 || k <= 0) return 0;
-    if (!make_plan(planes, H, W, k, true, &p)) return 0;
+    if (!make_plan(planes, H, W, k, true, false, &p)) return 0;
     return p.bytes;
 }
 
@@ -1159,7 +1062,7 @@ OG_API int og_hmp_nms_f32(const float *heat, long planes, int H, int W, float *o
     OG_REQUIRE((long)H * W < (1l << 27), OG_EINVAL, "%s: plane too large", name);
     Plan p;
     const bool aligned = (uintptr_t)heat % 16 == 0 && (uintptr_t)out % 16 == 0;
-    OG_REQUIRE(make_plan(planes, H, W, 1, aligned, &p), OG_EUNSUPPORTED, "%s: unsupported W=%d", name, W);
+    OG_REQUIRE(make_plan(planes, H, W, 1, aligned, false, &p), OG_EUNSUPPORTED, "%s: unsupported W=%d", name, W);
     const long total = planes * p.nbands;
     OG_REQUIRE(total < (1l << 30), OG_EINVAL, "%s: too many work items", name);
     const int padded = (int)((total + 7) / 8 * 8);
