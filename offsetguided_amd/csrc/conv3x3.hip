@@ -29,7 +29,6 @@
 //   that retires step s comes before the barrier, the reads after it; the stage refilled after the barrier is
 //   the one whose reads every wave finished (lgkmcnt(0)) before arriving.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -376,7 +375,6 @@ conv3x3_kernel(ConvArgs a)
     // (An agent-scope release fence per workgroup instead writes back the XCD's whole L2 each time: measured
     // 3-10x slower here.)  Correct for any placement of a tile's splits over XCDs.
     if (a.ksplit > 1) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const int tile = blockIdx.x;
         constexpr uint32_t kSlabBytes = NT * MT * 256 * 16;
         // descriptor and scalar offsets pinned to SGPRs (readfirstlane): left to the compiler they sat in VGPRs and every
@@ -408,10 +406,8 @@ conv3x3_kernel(ConvArgs a)
         // all loads of a batch are issued before the first add (one memory round trip per batch, not per slab);
         // slots past ksplit are read out of range, which a buffer load returns as 0
         // (64-wide tiles: 8 slabs = every plan's K split in ONE round trip; two dependent batches cost 2 us per layer)
-#ifndef OG_GATHER_SLABS
-#define OG_GATHER_SLABS 32
-#endif
-        constexpr int kBatch = NT * MT >= 16 ? 1 : OG_GATHER_SLABS / (NT * MT);
+        constexpr int kGatherSlabs = 32;
+        constexpr int kBatch = NT * MT >= 16 ? 1 : kGatherSlabs / (NT * MT);
         // the sum runs over ALL slabs in slice order, the own one re-read like the others: the result does not depend on which slice
         // happened to arrive last (fp32 addition is not associative: adding the others to the own registers made the layer -- and with
         // it the whole forward -- differ in the last bit from run to run; as in the tiled kernel's K split)
@@ -520,39 +516,35 @@ static inline int conv_out_dim(int in, int ksize, int stride) { return (in + 2 *
 OG_API void og_conv3x3_debug_stamps(void *buf) { g_stamps = (unsigned long long *)buf; }
 #endif
 
-OG_API size_t og_conv3x3_workspace_bytes(long pixels, int Cin, int Cout)
+// The validated plan behind the *_workspace_bytes entry points: 0 where the shape is refused or has no plan, else the exact
+// requirement of one layer (Cin2: channels of an appended 1x1 projection, or 0).
+static size_t plan_workspace_bytes(long N, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int Cin2)
 {
+    if (N <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || Cin2 < 0 || Cin2 % 64) return 0;
+    if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return 0;
+    const long M = N * conv_out_dim(Hin, ksize, stride) * conv_out_dim(Win, ksize, stride);
     Plan p;
-    if (pixels <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || !make_plan(pixels, Cin, Cout, p)) return 0;
-    return ws_layout(p, nullptr, nullptr);
+    return make_plan(M, Cin, Cout, p, ksize * ksize, Cin2 / 64) ? ws_layout(p, nullptr, nullptr) : 0;
 }
 
+OG_API size_t og_conv3x3_workspace_bytes(long pixels, int Cin, int Cout)
+{
+    return plan_workspace_bytes(pixels, 1, 1, Cin, Cout, 3, 1, 0);      // (a 1 x 1 image per "pixel": M = pixels)
+}
 
-// Exact requirement for one layer.
 OG_API size_t og_conv2d_workspace_bytes(int N, int Hin, int Win, int Cin, int Cout, int ksize, int stride)
 {
-    if (N <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64) return 0;
-    if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return 0;
-    const int H = conv_out_dim(Hin, ksize, stride), W = conv_out_dim(Win, ksize, stride);
-    const long M = (long)N * H * W;
-    Plan p;
-    if (!make_plan(M, Cin, Cout, p, ksize * ksize)) return 0;
-    return ws_layout(p, nullptr, nullptr);
+    return plan_workspace_bytes(N, Hin, Win, Cin, Cout, ksize, stride, 0);
 }
 
 OG_API size_t og_conv2d_proj_workspace_bytes(int N, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int Cin2)
 {
-    if (N <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || Cin2 <= 0 || Cin2 % 64) return 0;
-    if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return 0;
-    const long M = (long)N * conv_out_dim(Hin, ksize, stride) * conv_out_dim(Win, ksize, stride);
-    Plan p;
-    if (!make_plan(M, Cin, Cout, p, ksize * ksize, Cin2 / 64)) return 0;
-    return ws_layout(p, nullptr, nullptr);
+    return Cin2 > 0 ? plan_workspace_bytes(N, Hin, Win, Cin, Cout, ksize, stride, Cin2) : 0;
 }
 
 OG_API size_t og_conv3x3_workspace_bytes_nhw(int N, int H, int W, int Cin, int Cout)
 {
-    return og_conv2d_workspace_bytes(N, H, W, Cin, Cout, 3, 1);
+    return plan_workspace_bytes(N, H, W, Cin, Cout, 3, 1, 0);
 }
 
 #endif
@@ -588,7 +580,8 @@ static int conv_run(const char *name, const void *x, const void *w, const float 
     Plan p;
     OG_REQUIRE(make_plan(M, Cin, Cout, p, taps, pj.x2 ? pj.Cin2 / 64 : 0), OG_EUNSUPPORTED, "%s: no tile plan", name);
     OG_REQUIRE((size_t)p.m_tiles * p.n_tiles <= kMaxTiles, OG_EUNSUPPORTED, "%s: too many tiles", name);
-    const size_t need = ws_layout(p, nullptr, nullptr);
+    size_t c_off, s_off;
+    const size_t need = ws_layout(p, &c_off, &s_off);
     OG_REQUIRE(workspace_bytes >= need, OG_ENOSPC, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
 
     ConvArgs a = {};
@@ -598,8 +591,6 @@ static int conv_run(const char *name, const void *x, const void *w, const float 
     a.skip = (const unsigned short *)skip;
     a.out = (unsigned short *)out;
     a.zero = (const unsigned short *)workspace;  // first 256 B: zero page (workspace is zero-initialised by the caller)
-    size_t c_off, s_off;
-    ws_layout(p, &c_off, &s_off);
     a.counters = (int *)((char *)workspace + c_off);
     a.partial = (float *)((char *)workspace + s_off);
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.M = (int)M;
@@ -681,10 +672,8 @@ OG_API size_t og_conv3x3_tiled_workspace_bytes(int N, int H, int W, int Cin, int
 {
     const int kind = og_conv3x3_tiled_supported(N, H, W, Cin, Cout);
     if (!kind) return 0;
-    const long items = tiled_items(kind, N, H, W, Cout);
-    const int ks = tiled_ksplit(kind, items, Cin);
-    if (ks <= 1 || items > (long)kMaxTiles) return 0;
-    return kZeroPageBytes + kMaxTiles * sizeof(int) + (size_t)items * ks * tiled_slab_bytes(kind);
+    const Plan p = tiled_plan(kind, N, H, W, Cin, Cout);
+    return p.ksplit > 1 ? ws_layout(p, nullptr, nullptr) : 0;
 }
 
 OG_API int og_conv3x3_pack_w16(const void *w, int Cin, int Cout, int order, void *packed, void *stream)
@@ -703,61 +692,64 @@ OG_API int og_conv3x3_pack_w16(const void *w, int Cin, int Cout, int order, void
 #endif
 
 namespace {
+// What the two tiled entry points share: the shape and size checks (32-bit byte offsets) and the ConvArgs fields both kernels read.
+// H, W = output size.
+int tiled_fill(const char *name, ConvArgs &h, const void *x, const void *w_packed, const float *bias, const void *skip, void *out, int N,
+               int Hin, int Win, int stride, int Cin, int Cout, int relu)
+{
+    OG_REQUIRE(N > 0 && Hin > 0 && Win > 0 && Hin % stride == 0 && Win % stride == 0, OG_EINVAL, "%s: bad shape", name);
+    const int H = Hin / stride, W = Win / stride;
+    const long M = (long)N * H * W, Min = (long)N * Hin * Win;
+    OG_REQUIRE(Min * (long)Cin < (1l << 30) && M * (long)Cout < (1l << 30), OG_EUNSUPPORTED, "%s: tensor too large (>= 2 GiB)", name);
+    h.x = (const unsigned short *)x; h.w = (const unsigned short *)w_packed; h.bias = bias;
+    h.skip = (const unsigned short *)skip; h.out = (unsigned short *)out;
+    h.H = H; h.W = W; h.Hin = Hin; h.Win = Win; h.Cin = Cin; h.Cout = Cout; h.n_tiles = Cout / 128; h.relu = relu;
+    h.x_bytes = (int)(Min * Cin * 2);
+    h.w_bytes = Cout * 9 * Cin * 2;
+    return OG_OK;
+}
+
 int conv3x3_tiled_impl(const char *name, const void *x, const void *w_packed, const float *bias, const void *skip, void *out, void *up,
                        int N, int H, int W, int Cin, int Cout, int relu, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const OgWarm warm = og_take_warm_hint();      // (taken even when the launch is refused: a hint never outlives its call)
+    ConvArgs h = {};
+    h.warm = og_take_warm_hint();      // (taken even when the launch is refused: a hint never outlives its call)
     OG_REQUIRE(x && w_packed && bias && (out || up), OG_EINVAL, "%s: null pointer", name);
     OG_REQUIRE(!up || (uintptr_t)up % 16 == 0, OG_EINVAL, "%s: `up` must be 16-byte aligned", name);
-    OG_REQUIRE(N > 0 && H > 0 && W > 0, OG_EINVAL, "%s: bad shape", name);
-    const long M = (long)N * H * W;
-    OG_REQUIRE(M * (long)Cin < (1l << 30) && M * (long)Cout < (1l << 30), OG_EUNSUPPORTED, "%s: tensor too large (>= 2 GiB)", name);
+    const int rc = tiled_fill(name, h, x, w_packed, bias, skip, out, N, H, W, 1, Cin, Cout, relu);
+    if (rc != OG_OK) return rc;
     const int kind = tiled_kind(H, W, Cin, Cout);
     OG_REQUIRE(kind != 0, OG_EUNSUPPORTED, "%s: needs Cout %% 128 == 0, Cin %% 64 == 0 and H, W multiples of 16 or W == 40 with H %% 4 == 0 "
                "(got %dx%d, %d -> %d)", name, H, W, Cin, Cout);
-    ConvArgs h = {};
-    h.x = (const unsigned short *)x; h.w = (const unsigned short *)w_packed; h.bias = bias;
-    h.skip = (const unsigned short *)skip; h.out = (unsigned short *)out; h.up = (unsigned short *)up;
-    h.N = N; h.H = H; h.W = W; h.Cin = Cin; h.Cout = Cout; h.M = (int)M; h.n_tiles = Cout / 128; h.relu = relu;
-    h.Hin = H; h.Win = W; h.stride = 1; h.taps = 9;
-    h.x_bytes = (int)(M * Cin * 2);
-    h.w_bytes = Cout * 9 * Cin * 2;
+    h.up = (unsigned short *)up;
 #ifdef OG_TILED_STAMPS
     h.stamps = g_stamps;
 #endif
-    hipStream_t st = (hipStream_t)stream;
-    h.warm = warm;
-    const long items = tiled_items(kind, N, H, W, Cout);
-    h.ksplit = (items <= (long)kMaxTiles) ? tiled_ksplit(kind, items, Cin) : 1;
-    if (h.ksplit > 1) {
-        const size_t need = kZeroPageBytes + kMaxTiles * sizeof(int) + (size_t)items * h.ksplit * tiled_slab_bytes(kind);
+    const Plan p = tiled_plan(kind, N, H, W, Cin, Cout);
+    h.ksplit = p.ksplit;
+    if (p.ksplit > 1) {
+        size_t c_off, s_off;
+        const size_t need = ws_layout(p, &c_off, &s_off);
         OG_REQUIRE(workspace && workspace_bytes >= need, OG_ENOSPC, "%s: workspace %zu < %zu bytes (og_conv3x3_tiled_workspace_bytes)", name,
                    workspace ? workspace_bytes : (size_t)0, need);
         OG_REQUIRE((uintptr_t)workspace % 256 == 0, OG_EINVAL, "%s: workspace must be 256-byte aligned", name);
-        h.counters = (int *)((char *)workspace + kZeroPageBytes);
-        h.partial = (float *)((char *)workspace + kZeroPageBytes + kMaxTiles * sizeof(int));
+        h.counters = (int *)((char *)workspace + c_off);
+        h.partial = (float *)((char *)workspace + s_off);
     }
-#define TILED_LAUNCH(TW_, TH_, WM_, VAR_)                                                                             \
+    const dim3 grid((unsigned)(tiled_items(kind, N, H, W, Cout) * p.ksplit));
+#define TILED_LAUNCH(KIND_)                                                                                           \
     do {                                                                                                              \
-        constexpr int halo_ = ((TW_ + 2) * (TH_ + 2) * 5 * 16 + 1023) / 1024 * 1024;                                  \
-        const int lds_ = 2 * halo_ + (TW_ == 20 ? OG_TILED_RING20 : TW_ == 40 ? OG_TILED_RING40 : 3) * 128 * 64 + 1024; \
+        constexpr TiledShape s_ = kTiledShapes[KIND_];                                                                \
+        constexpr int lds_ = tiled_lds_bytes(s_.tw, s_.th);                                                           \
         static OgAttrOnce attr_;                                                                                      \
         if (attr_.need())                                                                                             \
-            (void)hipFuncSetAttribute((const void *)conv3x3_tiled_kernel<TW_, TH_, WM_, VAR_, 4>,                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                        \
-        const long blocks_ = (long)N * (H / TH_) * (W / TW_) * h.n_tiles * h.ksplit;                                  \
-        hipLaunchKernelGGL((conv3x3_tiled_kernel<TW_, TH_, WM_, VAR_, 4>), dim3((unsigned)blocks_), dim3(256), lds_, st, h); \
+            (void)hipFuncSetAttribute((const void *)conv3x3_tiled_kernel<s_.tw, s_.th, s_.wm>,                        \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                              \
+        hipLaunchKernelGGL((conv3x3_tiled_kernel<s_.tw, s_.th, s_.wm>), grid, dim3(256), lds_, (hipStream_t)stream, h); \
     } while (0)
-    // VAR 26 = 16 (next step's weight fragments in rotating register sets; the step's DMA issue and every fragment read BETWEEN its MFMAs,
-    // one item per gap: round 5, -2 % of the network step) + 8 + 2 (what 16 replaces: LDS-DMA issue behind the fragment reads; the other
-    // tuning variants -- weight-fragment prefetch, 2 x 2 waves, 8 waves, 20 x 4 tiles at 40x40, no XCD remap, the timing-only ablations --
-    // are described in EXPERIMENTS.md)
-#ifndef OG_TILED_VAR16
-#define OG_TILED_VAR16 26
-#endif
-    if (kind == 1) TILED_LAUNCH(16, 16, 4, OG_TILED_VAR16);
-    else if (kind == 3) TILED_LAUNCH(20, 4, 1, 2);
-    else TILED_LAUNCH(40, 4, 2, 2);
+    if (kind == 1) TILED_LAUNCH(1);
+    else if (kind == 2) TILED_LAUNCH(2);
+    else TILED_LAUNCH(3);
 #undef TILED_LAUNCH
     OG_LAUNCH_CHECK(name);
     return OG_OK;
@@ -791,35 +783,26 @@ OG_API int OG_LP_NAME(og_conv3x3s2_tiled)(const void *x, const void *w_packed, c
 {
     const char *name = OG_LP_STR("og_conv3x3s2_tiled");
     OG_REQUIRE(x && w_packed && bias && out, OG_EINVAL, "%s: null pointer", name);
-    OG_REQUIRE(N > 0 && Hin > 0 && Win > 0 && !(Hin & 1) && !(Win & 1), OG_EINVAL, "%s: bad shape", name);
-    const int H = Hin / 2, W = Win / 2;
-    const long M = (long)N * H * W, Min = (long)N * Hin * Win;
-    OG_REQUIRE(Min * (long)Cin < (1l << 30) && M * (long)Cout < (1l << 30), OG_EUNSUPPORTED, "%s: tensor too large (>= 2 GiB)", name);
+    ConvArgs h = {};
+    const int rc = tiled_fill(name, h, x, w_packed, bias, skip, out, N, Hin, Win, 2, Cin, Cout, relu);
+    if (rc != OG_OK) return rc;
     const int kind = og_conv3x3s2_tiled_supported(N, Hin, Win, Cin, Cout);
     OG_REQUIRE(kind != 0, OG_EUNSUPPORTED,
                "%s: needs Cout %% 128 == 0, Cin %% 64 == 0 and an output of 8k x 16k pixels or 2k x 40 (got %dx%d -> %dx%d, %d -> %d)", name,
-               Hin, Win, H, W, Cin, Cout);
-    ConvArgs h = {};
+               Hin, Win, h.H, h.W, Cin, Cout);
     h.warm = og_take_warm_hint();
-    h.x = (const unsigned short *)x; h.w = (const unsigned short *)w_packed; h.bias = bias;
-    h.skip = (const unsigned short *)skip; h.out = (unsigned short *)out;
-    h.N = N; h.H = H; h.W = W; h.Cin = Cin; h.Cout = Cout; h.M = (int)M; h.n_tiles = Cout / 128; h.relu = relu;
-    h.Hin = Hin; h.Win = Win; h.stride = 2; h.taps = 9;
-    h.x_bytes = (int)(Min * Cin * 2);
-    h.w_bytes = Cout * 9 * Cin * 2;
-    constexpr int lds_ = 3 * 128 * 64 + 3 * 3 * 4096;
-#define S2_LAUNCH(TW_, TH_, WM_, VAR_)                                                                                \
+#define S2_LAUNCH(TW_, TH_, WM_)                                                                                      \
     do {                                                                                                              \
         static OgAttrOnce attr_;                                                                                      \
         if (attr_.need())                                                                                             \
-            (void)hipFuncSetAttribute((const void *)conv3x3s2_tiled_kernel<TW_, TH_, WM_, VAR_>,                      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                              \
-        const long blocks_ = (long)N * (H / TH_) * (W / TW_) * h.n_tiles;                                             \
-        hipLaunchKernelGGL((conv3x3s2_tiled_kernel<TW_, TH_, WM_, VAR_>), dim3((unsigned)blocks_), dim3(256), lds_,   \
+            (void)hipFuncSetAttribute((const void *)conv3x3s2_tiled_kernel<TW_, TH_, WM_>,                            \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, kS2LdsBytes);                       \
+        const long blocks_ = (long)N * (h.H / TH_) * (h.W / TW_) * h.n_tiles;                                         \
+        hipLaunchKernelGGL((conv3x3s2_tiled_kernel<TW_, TH_, WM_>), dim3((unsigned)blocks_), dim3(256), kS2LdsBytes,  \
                            (hipStream_t)stream, h);                                                                   \
     } while (0)
-    if (kind == 2) S2_LAUNCH(40, 2, 1, 2);
-    else S2_LAUNCH(16, 8, 2, 2);       // DMA issue behind the fragment reads: measured 1-4 % faster
+    if (kind == 2) S2_LAUNCH(40, 2, 1);
+    else S2_LAUNCH(16, 8, 2);
 #undef S2_LAUNCH
     OG_LAUNCH_CHECK(name);
     return OG_OK;
@@ -855,15 +838,30 @@ static int pw_fill(const char *name, PwArgs &a, const void *x1, int C1, int H1, 
 }
 
 // Workgroups of a pointwise launch: every item its own workgroup, or -- where the items outnumber the chip's slots -- the persistent
-// form: OG_PW_PERSIST workgroups per CU (default 2 = the kernel's occupancy; 0 = off), rounded down to a multiple of 8 x n_tiles so that a
-// workgroup keeps its XCD's range of items and its cout tile.
+// form: two workgroups per CU (the kernel's occupancy), rounded down to a multiple of 8 x n_tiles so that a workgroup keeps its XCD's
+// range of items and its cout tile.
 static long pw_blocks(const PwArgs &a)
 {
-    static const int per_cu = [] { const char *e = getenv("OG_PW_PERSIST"); return e ? atoi(e) : 2; }();
+    constexpr int kPerCu = 2;
     const long unit = 8l * a.n_tiles;
-    long cap = (long)per_cu * og_cu_count() / unit * unit;
-    if (per_cu <= 0 || cap <= 0 || a.items <= cap || a.items % 8 != 0) return a.items;
+    const long cap = (long)kPerCu * og_cu_count() / unit * unit;
+    if (cap <= 0 || a.items <= cap || a.items % 8 != 0) return a.items;
     return cap;
+}
+
+// One pointwise launch: two pixel register sets in turn (D = 2) where the number of 64-channel steps is even, else one.
+template <int BN, int MODE>
+static void pw_launch(const PwArgs &a, long blocks, int lds_bytes, void *stream)
+{
+    static OgAttrOnce attr_;
+    if (lds_bytes > 64 * 1024 && attr_.need()) {
+        (void)hipFuncSetAttribute((const void *)conv1x1_tiled_kernel<BN, MODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        (void)hipFuncSetAttribute((const void *)conv1x1_tiled_kernel<BN, MODE, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    }
+    if (((a.C1 + a.C2) >> 6) % 2 == 0)
+        hipLaunchKernelGGL((conv1x1_tiled_kernel<BN, MODE, 2>), dim3((unsigned)blocks), dim3(256), lds_bytes, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((conv1x1_tiled_kernel<BN, MODE, 1>), dim3((unsigned)blocks), dim3(256), lds_bytes, (hipStream_t)stream, a);
 }
 
 OG_API int OG_LP_NAME(og_conv1x1_tiled)(const void *x1, int C1, int H1, int W1, int stride1, const void *x2, int C2, int H2, int W2,
@@ -878,16 +876,7 @@ OG_API int OG_LP_NAME(og_conv1x1_tiled)(const void *x1, int C1, int H1, int W1, 
     a.skip = (const unsigned short *)skip; a.out = (unsigned short *)out; a.relu = relu;
     constexpr int lds_ = 256 * (2 * 128 + 16);     // the output tile's staging (68 KiB) > the weight ring (48 KiB); two workgroups per CU
     static_assert(lds_ >= 3 * 2 * 128 * 64 && 2 * lds_ <= 160 * 1024, "LDS");
-    static OgAttrOnce attr_;
-    if (attr_.need()) {
-        (void)hipFuncSetAttribute((const void *)conv1x1_tiled_kernel<128, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_);
-        (void)hipFuncSetAttribute((const void *)conv1x1_tiled_kernel<128, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_);
-    }
-    const long blocks = pw_blocks(a);
-    if (((a.C1 + a.C2) >> 6) % 2 == 0)     // two pixel register sets in turn: an even number of 64-channel steps
-        hipLaunchKernelGGL((conv1x1_tiled_kernel<128, 0, 2>), dim3((unsigned)blocks), dim3(256), lds_, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((conv1x1_tiled_kernel<128, 0, 1>), dim3((unsigned)blocks), dim3(256), lds_, (hipStream_t)stream, a);
+    pw_launch<128, 0>(a, pw_blocks(a), lds_, stream);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }
@@ -914,11 +903,7 @@ OG_API int OG_LP_NAME(og_conv1x1_heads)(const void *x, int C, const void *w_pack
     for (int i = n_heads; i < 4; ++i) a.first[i] = c;     // empty ranges
     OG_REQUIRE(c <= Cout, OG_EINVAL, "%s: the heads have %d channels, the packed weight %d", name, c, Cout);
     constexpr int lds_ = 3 * 2 * 64 * 64;
-    const long blocks = a.items;        // (the persistent form loses here: 51.5 vs 49.4 us -- no output staging to overlap, a 64-cout tile)
-    if ((a.C1 >> 6) % 2 == 0)
-        hipLaunchKernelGGL((conv1x1_tiled_kernel<64, 1, 2>), dim3((unsigned)blocks), dim3(256), lds_, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((conv1x1_tiled_kernel<64, 1, 1>), dim3((unsigned)blocks), dim3(256), lds_, (hipStream_t)stream, a);
+    pw_launch<64, 1>(a, a.items, lds_, stream);        // (the persistent form loses here: 51.5 vs 49.4 us -- no output staging to overlap, a 64-cout tile)
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }

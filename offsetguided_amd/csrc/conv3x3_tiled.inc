@@ -1,8 +1,7 @@
-// Halo-tiled 3x3 convolution, second generation ("tiled"): TWO independent 4-wave workgroups per CU instead of one
-// 8-wave workgroup that owns the CU (conv3x3_halo_kernel above).  Included by conv3x3.hip (namespace-scope code first,
-// then the C ABI).
+// Halo-tiled 3x3 convolution ("tiled"): TWO independent 4-wave workgroups per CU instead of one 8-wave workgroup that owns
+// the CU (the first halo kernel; DESIGN.md section 4, C1).  Included by conv3x3.hip (namespace-scope code first, then the C ABI).
 //
-// What the first kernel's measurements said (DESIGN.md section 4, C1): per work item 1.2 us set-up + 6-8.5 us wait for the
+// What the first kernel's measurements said: per work item 1.2 us set-up + 6-8.5 us wait for the
 // first halo / weight tiles + 3.1 us epilogue around a 29-31 us main loop, with nothing else resident on the CU to use
 // the matrix pipe meanwhile (160 KiB of LDS per workgroup); 16 ds_read_b128 per 32 MFMA with a 2-way bank conflict on the
 // padded halo image (34 % of the LDS-active cycles); two barriers per 32-MFMA phase for the hand-made ping-pong of the two
@@ -67,55 +66,120 @@ conv3x3_pack_kernel(const unsigned short *w, unsigned short *packed, int Cin, in
     *reinterpret_cast<u16x8 *>(packed + slot * 8) = v;
 }
 
-// VAR: the tuning switches that are still instantiated both ways by tools/build_variants.sh -DOG_TILED_VAR16=...: 1 = no s_setprio
-// around the MFMA block (+3 %), 2 = LDS-DMA issue behind the fragment reads instead of in front of them (-1..-2 %), 4 = no XCD-aware
-// work order (+1 %), 16 = weight fragments a step ahead in rotating register sets + every issue item of the step BETWEEN its MFMAs (the
-// product at 16 x 16 tiles: 26; the 40 x 4 / 20 x 4 forms always, with two full sets).  (Bit 3 was the first cut of that order -- this
-// step's own weight fragments, two of them in front of the MFMA block: -0.8...-1.4 % of the network step; bit 4 another -0.6 %.)  The other variants and the timing-only ablations of round 3 (weight fragments a step ahead
-// over a half-stage-staggered ring, no DMA / no barrier / fragments read once / relaxed waits) are described in DESIGN.md section 4
-// and EXPERIMENTS.md; their code left the kernel in round 4.
-// NW: waves per workgroup (4: one per SIMD, 64 x 128 or 128 x 64 outputs per wave, <= 256 registers; the 8-wave forms lost their A/Bs).
-// (A chained launch -- the workgroups of up to four dependent layers in one grid, a workgroup of layer l waiting for the arrival
-// counters of the <= 9 pixel tiles of layer l - 1 under its halo -- was built in round 4: -9 % on two 160x160 residual blocks
-// alone, nothing in the network; tools/experiments/conv3x3_tiled_chain.patch.)
-template <int TW, int TH, int WM, int VAR, int NW>
+// Pixel fragment of the tiled kernels: two ds_read_b64 per lane (k = 4 fk .. 4 fk + 3 and 16 + 4 fk ..), written as inline asm -- left
+// to the compiler the pair becomes ONE ds_read2_b64 (two accesses 32 B apart), which runs at half the rate and banks modulo 32 dwords
+// (MI355X_MICROARCH, LDS).  The compiler does not count these reads: their consumer is the MFMA block of the NEXT step, behind that
+// step's lgkmcnt(0) (wait_vm_lgkm0) -- nothing else may touch the result in between (hence no register copies at a chunk seam).
+template <int IMM>
+__device__ __forceinline__ bf16x8 ds_read_b64_pair(uint32_t addr)
+{
+    typedef unsigned long long u64;
+    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+    u64 lo, hi;
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "i"(IMM));
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "i"(IMM + 32));
+    u64x2 v;
+    v[0] = lo;
+    v[1] = hi;
+    return __builtin_bit_cast(bf16x8, v);
+}
+
+// ---- tile shapes ------------------------------------------------------------------------------------------------
+// The stride-1 kernel's forms, indexed by `kind` (tiled_kind: what og_conv3x3_tiled_supported returns): tile width and height in pixels,
+// waves along the pixels (4 / wm along the couts), stages of the weight ring.
+// ring: 3 stages where a step is 32 MFMA per wave (16 x 16 tiles: two steps cover the L2 latency); 6 at the 20-wide level, whose steps
+// are 10 MFMA per wave = 70 ns: with two steps of look-ahead every step waited for most of an L2 round trip; 4 at the 40-wide level.
+struct TiledShape {
+    int tw, th, wm, ring;
+};
+constexpr TiledShape kTiledShapes[4] = {{0, 0, 0, 0}, {16, 16, 4, 3}, {40, 4, 2, 4}, {20, 4, 1, 6}};
+constexpr int tiled_ring(int tw)
+{
+    for (const TiledShape &s : kTiledShapes)
+        if (s.tw == tw) return s.ring;
+    return 0;
+}
+// LDS of a workgroup: [weight ring | two halo images of a 32-channel chunk, 80 B per pixel, whole KiB | 1 KiB dump]
+constexpr int tiled_halo_bytes(int tw, int th) { return ((tw + 2) * (th + 2) * 5 * 16 + 1023) / 1024 * 1024; }
+constexpr int tiled_lds_bytes(int tw, int th) { return tiled_ring(tw) * 128 * 64 + 2 * tiled_halo_bytes(tw, th) + 1024; }
+// the stride-2 kernel: the weight ring + a ring of three phase images of three 4-KiB pieces
+constexpr int kS2LdsBytes = 3 * 128 * 64 + 3 * 3 * 4096;
+
+// 1 = 16 x 16 (H, W multiples of 16), 2 = 40 x 4 (W == 40, H % 4 == 0), 3 = 20 x 4 (W == 20, H % 4 == 0), 0 = none
+static int tiled_kind(int H, int W, int Cin, int Cout)
+{
+    if (Cout % 128 || Cin % 64) return 0;
+    if (H % 16 == 0 && W % 16 == 0) return 1;
+    for (int k = 2; k <= 3; ++k)      // one tile across
+        if (W == kTiledShapes[k].tw && H % kTiledShapes[k].th == 0) return k;
+    return 0;
+}
+static long tiled_items(int kind, int N, int H, int W, int Cout)
+{
+    return (long)N * (H / kTiledShapes[kind].th) * (W / kTiledShapes[kind].tw) * (Cout / 128);
+}
+
+// K slices for a level with few output tiles (< 200 workgroups against the chip's 512 slots), from the measurements of
+// profiles/r03_ksplit.log (batch 8, us per layer, 1 / 2 / 3 slices):
+//   40x40 384->256 (160 tiles of 40x4):  37.8 / 37.6 / 33.4    -> 3 slices where the chunks divide by 6
+//   40x40 256->256 (160 tiles, 8 chunks): 27.4 / 30.5 / --      -> no split (320 workgroups do not pay for 80 KiB slabs)
+//   40x40 384->384 (240 tiles):           43.5 / 43.9 / 51.7    -> no split: that level moves 7.8 KB of LDS-DMA per MFLOP
+//                                                                  and sits at the ~7 TB/s the L2 -> LDS path delivers either way
+//   20x20 384->384 (120 tiles of 20x4):   25.0 / 20.0 / 20.4    -> 2 slices (the split-K GEMM kernel: 21.6)
+// A slice always has an even number of chunks.
+static int tiled_ksplit(int kind, long items, int Cin)
+{
+    const int chunks = Cin / 32;
+    if (items >= 200) return 1;
+    if (kind == 3) return chunks % 4 == 0 ? 2 : 1;
+    if (kind == 2) return chunks % 6 == 0 ? 3 : 1;
+    return 1;
+}
+// The K split in the terms of ws_layout: the work items are the tiles, a slab holds a tile's tw * th pixels x 128 couts in fp32
+// (a split has fewer than 200 items: far below kMaxTiles).
+static Plan tiled_plan(int kind, int N, int H, int W, int Cin, int Cout)
+{
+    const long items = tiled_items(kind, N, H, W, Cout);
+    Plan p = {};
+    p.ksplit = tiled_ksplit(kind, items, Cin);
+    p.bm = kTiledShapes[kind].tw * kTiledShapes[kind].th;
+    p.bn = 128;
+    p.m_tiles = p.ksplit > 1 ? (int)items : 0;
+    p.n_tiles = 1;
+    return p;
+}
+
+// Every wave of the four (one per SIMD) owns 64 x 128 or 128 x 64 outputs in <= 256 registers.  The schedule of a step is fixed per tile
+// width (kWfRot below); the tuning variants that lost their A/Bs -- no s_setprio, DMA issue in front of the fragment reads, no XCD-aware
+// order, weight fragments read in the step that uses them, 8-wave workgroups, the timing-only ablations, a chained launch of dependent
+// layers (tools/experiments/conv3x3_tiled_chain.patch) -- are described in EXPERIMENTS.md and DESIGN.md section 4.
+template <int TW, int TH, int WM>
 __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int bid, const int nblk)
 {
-    constexpr int BN = 128, WN = NW / WM, kThr = 64 * NW, kPieceB = kThr * 16;
+    constexpr int BN = 128, WN = 4 / WM, kThr = 256, kPieceB = kThr * 16;
     constexpr int kHaloW = TW + 2, kHaloPx = (TW + 2) * (TH + 2), kPitch = 80;
     constexpr int NPA = (kHaloPx * 5 + kThr - 1) / kThr;     // halo DMA pieces per thread and chunk (5 slots per pixel)
     // halo buffer: the pieces' 1-KiB wave blocks up to the one that holds the last slot; the blocks of the last piece that
-    // lie beyond it (8-wave form: six of eight) go to a shared 1-KiB dump region (zeros from out-of-range lanes)
-    constexpr int kABytes = (kHaloPx * 5 * 16 + 1023) / 1024 * 1024, kBBytes = BN * 64;
-    // weight ring: a step's stage is issued kAhead = kRing - 1 steps before its use.  3 stages where a step is 32 MFMA per wave (16 x 16
-    // tiles: two steps cover the L2 latency); OG_TILED_RING20 (6) at the 20-wide level, whose steps are 10 MFMA per wave = 70 ns: with two
-    // steps of look-ahead every step waited for most of an L2 round trip
-#ifndef OG_TILED_RING20
-#define OG_TILED_RING20 6
-#endif
-    // kWfAhead (20-wide level): the weight FRAGMENTS of step s + 1 are read during the MFMAs of step s, like the pixel fragments (a step of
+    // lie beyond it go to a shared 1-KiB dump region (zeros from out-of-range lanes)
+    constexpr int kABytes = tiled_halo_bytes(TW, TH), kBBytes = BN * 64;
+    // weight ring (tiled_ring): the weight FRAGMENTS of step s + 1 are read during the MFMAs of step s, like the pixel fragments (a step of
     // 10 MFMA per wave does not cover the LDS latency of its own fragment reads); the stage of step s is then free behind the barrier of
-    // step s, and a stage is issued kRing steps ahead
-#ifndef OG_TILED_RING40
-#define OG_TILED_RING40 4
-#endif
-    constexpr int kRing = TW == 20 ? OG_TILED_RING20 : TW == 40 ? OG_TILED_RING40 : 3;
-    // kWfRot (OG_TILED_VAR16 bit 4, 16 x 16 tiles: the product): the same with NT + 1 fragment register sets used in rotation instead of 2 NT
-    // (250 of 256 VGPRs are taken) -- fragment n of step s + 1 goes where fragment n - 1 of step s was, right behind the last MFMA that read
-    // it, fragment 0 into the spare set; the ring stays at 3 stages (a stage is free behind its own step's barrier: same look-ahead)
-    constexpr bool kWfRot = TW == 16 && (VAR & 16) != 0;
-    constexpr bool kWfAhead = kRing > 3 || kWfRot;
-    constexpr int kAhead = kWfAhead ? kRing : kRing - 1;
-    constexpr int kWin = kWfAhead ? kAhead - 2 : kAhead - 1;      // steps whose DMA may still be in flight behind a step's wait
-    // the ring slot of step (chunk q, tap): 9 q + tap mod kRing is a compile-time function of (q & 1, tap) for 3, 6 and 9 stages; with 4
+    // step s, and a stage is issued kAhead = kRing steps before its use
+    constexpr int kRing = tiled_ring(TW);
+    // kWfRot (16 x 16 tiles): NT + 1 fragment register sets used in rotation instead of 2 NT (250 of 256 VGPRs are taken) -- fragment n of
+    // step s + 1 goes where fragment n - 1 of step s was, right behind the last MFMA that read it, fragment 0 into the spare set
+    constexpr bool kWfRot = TW == 16;
+    constexpr int kAhead = kRing;
+    constexpr int kWin = kRing - 2;      // steps whose DMA may still be in flight behind a step's wait
+    // the ring slot of step (chunk q, tap): 9 q + tap mod kRing is a compile-time function of (q & 1, tap) for 3 and 6 stages; with 4
     // stages it is that function XOR 2 in every other chunk PAIR (18 = 2 mod 4): the two halves of the ring swap per pair (ring_off below)
-    static_assert(kRing == 3 || kRing == 4 || kRing == 6 || kRing == 9, "ring sizes the slot arithmetic serves");
+    static_assert(kRing == 3 || kRing == 4 || kRing == 6, "ring sizes the slot arithmetic serves");
     constexpr int kDump = kRing * kBBytes + 2 * kABytes;
     constexpr int PW = kBBytes / kPieceB;                    // weight pieces per thread per step
     constexpr int MT = TW * TH / 16 / WM, NT = 8 / WN;
-    static_assert(TW * TH % (16 * WM) == 0 && NW % WM == 0 && 8 % WN == 0 && PW >= 1, "unsupported tile");
+    static_assert(TW * TH % (16 * WM) == 0 && 4 % WM == 0 && 8 % WN == 0 && PW >= 1, "unsupported tile");
     static_assert(NPA <= 8 - kWin, "the last halo piece must be older than everything tap 8's wait leaves in flight (the steps 8 - kWin .. 7)");
-    static_assert(kDump + 1024 <= 80 * 1024, "two workgroups per CU");
+    static_assert(kDump + 1024 == tiled_lds_bytes(TW, TH) && kDump + 1024 <= 80 * 1024, "what the launcher asks for; two workgroups per CU");
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     unsigned char *const bufB = lds, *const bufA = lds + kRing * kBBytes;   // [B0 B1 B2 | A0 A1]: all read offsets < 64 KiB
 
@@ -130,7 +194,7 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
 #endif
     // XCD-aware order: the hardware deals workgroup ids round-robin over the 8 XCDs; consecutive WORK items (the cout
     // tiles of one pixel tile, then the neighbouring pixel tiles: shared halo, shared weights) go to one XCD's L2
-    const int wid = ((nblk & 7) == 0 && !(VAR & 4)) ? og_xcd_remap(bid, nblk) : bid;
+    const int wid = (nblk & 7) == 0 ? og_xcd_remap(bid, nblk) : bid;
     // K split (a.ksplit > 1, levels whose tiles would not fill the chip): consecutive work ids are the K slices of one
     // output tile; slice `split` runs chunks [q0, q_end) and the slices meet in the last arriver (below)
     const int ksplit = a.ksplit, item = wid / ksplit, split = wid - item * ksplit;
@@ -182,12 +246,7 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
         px_off[m] = ((lp / TW) * kHaloW + lp % TW) * kPitch + fk * 8;
     }
 
-    // Pixel fragments: two ds_read_b64 per lane, written as inline asm -- left to the compiler the pair becomes ONE
-    // ds_read2_b64 (two accesses 32 B apart), which runs at half the rate and banks modulo 32 dwords (MI355X_MICROARCH, LDS).
-    // The compiler does not count these reads: their consumer is the MFMA block of the NEXT step, behind that step's
-    // lgkmcnt(0) (wait_vm_lgkm0) -- nothing else may touch pf[] in between (hence no register copies at a chunk seam).
-    typedef unsigned long long u64;
-    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+    // pixel fragments (ds_read_b64_pair)
     const uint32_t lds_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)bufA;
     uint32_t px_addr[TW == 16 ? 1 : MT];
 #pragma unroll
@@ -196,14 +255,7 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
         constexpr int OFF = decltype(off_tag)::value, m = decltype(m_tag)::value;
         // TW == 16: the fragments of a wave are consecutive tile rows -> one address register, immediates for the rest
         constexpr int imm = OFF + (TW == 16 ? m * kHaloW * kPitch : 0);
-        const uint32_t addr = px_addr[TW == 16 ? 0 : m] + buf_off;
-        u64 lo, hi;
-        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "i"(imm));
-        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "i"(imm + 32));
-        u64x2 v;
-        v[0] = lo;
-        v[1] = hi;
-        pf[m] = __builtin_bit_cast(bf16x8, v);
+        pf[m] = ds_read_b64_pair<imm>(px_addr[TW == 16 ? 0 : m] + buf_off);
     };
     auto read_px = [&](auto off_tag, uint32_t buf_off, bf16x8 (&pf)[MT]) {
         og_static_for<MT>([&](auto m_tag) { read_px1(m_tag, off_tag, buf_off, pf); });
@@ -259,7 +311,7 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
 
     constexpr int kSets = NT == 8 ? 9 : NT == 4 ? 6 : 3, kFree = kSets - NT;      // (18 NT) mod kSets == 0: the rotation closes over a chunk pair
     static_assert(!kWfRot || ((18 * NT) % kSets == 0 && kFree >= 1 && NT * (MT - 1) >= kFree + 1 + MT), "rotating fragment sets");
-    bf16x8 pf[2][MT], wf[kWfAhead && !kWfRot ? 2 : 1][kWfRot ? kSets : NT];
+    bf16x8 pf[2][MT], wf[kWfRot ? 1 : 2][kWfRot ? kSets : NT];
 #ifdef OG_TILED_STAMPS
     // diagnostic build (tools/c1_stamps.py): per wave, shader-clock sums of the three phases of a step -- counted wait | barrier |
     // fragment reads + DMA issue + MFMA block -- from s_memtime marks whose results are collected behind the NEXT step's
@@ -288,10 +340,8 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
     }
 #endif
     read_px(std::integral_constant<int, 0>(), 0u, pf[0]);
-    if constexpr (kWfAhead) {
 #pragma unroll
-        for (int n = 0; n < NT; ++n) wf[0][n] = *reinterpret_cast<const bf16x8 *>(bufB + w_rd + n * 1024);
-    }
+    for (int n = 0; n < NT; ++n) wf[0][n] = *reinterpret_cast<const bf16x8 *>(bufB + w_rd + n * 1024);
 
     // One chunk = 9 steps.  MORE: a chunk follows (its halo trickles in during taps 0..NPA-1, weights(s+2) always exist);
     // the last chunk stops issuing at its last two steps.  PAR: the fragment set of the chunk's first step (9 is odd, so
@@ -306,7 +356,7 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
             const int s = q * 9 + tap;
             // weights(s) were issued kAhead steps ago;
             // lgkmcnt(0): the pixel fragments of this step (read during the previous one) are in their registers
-            // younger than the stage this step needs (weights(s); weights(s + 1) with kWfAhead) = what the steps s - kWin .. s - 1 issued: a
+            // younger than the stage this step needs (weights(s + 1)) = what the steps s - kWin .. s - 1 issued: a
             // halo piece each where the step is one of the first NPA of a chunk that has a successor (the steps of the chunk BEFORE this one
             // that fall in the window are its last kWin: none of them issues a halo piece), a weight stage each where step + kAhead exists
             {
@@ -341,12 +391,11 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
                 // = PAR: a slice starts at an even chunk)
                 if (MORE || tap + kAhead < 9) issue_b(s + kAhead, ring_off((kSlot0 + tap + kAhead) % kRing));
             };
-            const unsigned char *wB = bufB + ring_off((kSlot0 + tap + (kWfAhead ? 1 : 0)) % kRing);
-            constexpr int wcur = kWfAhead ? (PAR + tap) & 1 : 0, wnxt = kWfAhead ? (PAR + tap + 1) & 1 : 0;
+            const unsigned char *wB = bufB + ring_off((kSlot0 + tap + 1) % kRing);      // the NEXT step's stage
             if constexpr (kWfRot) {
                 constexpr bool kNext = MORE || tap < 8;
                 constexpr int t18 = PAR * 9 + tap, cur = (PAR + tap) & 1, nxt = cur ^ 1;
-                if (!(VAR & 1)) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 og_static_for<NT * MT>([&](auto i_tag) {
                     constexpr int i = decltype(i_tag)::value, n = i / MT, m = i % MT;
                     acc[n][m] = OG_LP_MFMA(wf[0][(t18 * NT + n) % kSets], pf[cur][m], acc[n][m]);
@@ -371,18 +420,18 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                if (!(VAR & 1)) __builtin_amdgcn_s_setprio(0);
-            } else if constexpr (kWfAhead) {
+                __builtin_amdgcn_s_setprio(0);
+            } else {
                 // Every fragment this step reads is the NEXT step's: the reads and the DMA issue go BETWEEN this step's MFMAs (one item
                 // behind each of the first 1 + MT + NT: an MFMA holds the vector issue for 8 of its 16 cycles), instead of in front of
                 // them -- with one wave per SIMD (this level has fewer workgroups than the chip has CUs) nothing else hides their issue time
                 static_assert(NT * MT >= 1 + MT + NT, "an MFMA gap per issue item");
                 constexpr bool kNext = MORE || tap < 8;
                 constexpr int cur = (PAR + tap) & 1, nxt = cur ^ 1;
-                if (!(VAR & 1)) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 og_static_for<NT * MT>([&](auto i_tag) {
                     constexpr int i = decltype(i_tag)::value, n = i / MT, m = i % MT;
-                    acc[n][m] = OG_LP_MFMA(wf[wcur][n], pf[cur][m], acc[n][m]);
+                    acc[n][m] = OG_LP_MFMA(wf[cur][n], pf[cur][m], acc[n][m]);
                     if constexpr (i == 0) {
                         issue_dma();
                     } else if constexpr (i - 1 < MT) {
@@ -392,28 +441,11 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
                         else if constexpr (MORE)
                             read_px1(std::integral_constant<int, i - 1>(), std::integral_constant<int, 0>(), nxt_off, pf[nxt]);
                     } else if constexpr (i - 1 - MT < NT) {
-                        if constexpr (kNext) wf[wnxt][i - 1 - MT] = *reinterpret_cast<const bf16x8 *>(wB + w_rd + (i - 1 - MT) * 1024);
+                        if constexpr (kNext) wf[nxt][i - 1 - MT] = *reinterpret_cast<const bf16x8 *>(wB + w_rd + (i - 1 - MT) * 1024);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                if (!(VAR & 1)) __builtin_amdgcn_s_setprio(0);
-            } else {
-            if (!(VAR & 2)) issue_dma();
-            // pixels of the NEXT step while this step's MFMAs run (tap 8: tap 0 of the next chunk's halo, complete since
-            // this step's wait)
-            if constexpr (tap < 8)
-                read_px(std::integral_constant<int, (((tap + 1) / 3) * kHaloW + (tap + 1) % 3) * kPitch>(), cur_off, pf[(PAR + tap + 1) & 1]);
-            else if constexpr (MORE)
-                read_px(std::integral_constant<int, 0>(), nxt_off, pf[(PAR + tap + 1) & 1]);
-#pragma unroll
-            for (int n = 0; n < NT; ++n) wf[0][n] = *reinterpret_cast<const bf16x8 *>(wB + w_rd + n * 1024);
-            if (VAR & 2) issue_dma();
-            if (!(VAR & 1)) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[n][m] = OG_LP_MFMA(wf[wcur][n], pf[(PAR + tap) & 1][m], acc[n][m]);
-            if (!(VAR & 1)) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
             }
 #ifdef OG_TILED_STAMPS
             asm volatile("s_memtime %0" : "=s"(st_end));
@@ -458,7 +490,6 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
     // write-through (sc1) stores -> vmcnt(0) -> barrier -> relaxed agent-scope ticket; the slice that arrives last adds the
     // others' slabs (sc1 loads, one slab per round trip) and runs the epilogue.  Correct for any placement over XCDs.
     if (ksplit > 1) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         constexpr int F = NT * MT;
         constexpr uint32_t kSlabBytes = F * kThr * 16;
         uint64_t slab_base = reinterpret_cast<uint64_t>(a.partial) + (uint64_t)item * ksplit * kSlabBytes;
@@ -572,11 +603,11 @@ __device__ __forceinline__ void conv3x3_tiled_body(const ConvArgs &a, const int 
     og_warm_sink(warm_v);
 }
 
-template <int TW, int TH, int WM, int VAR = 0, int NW = 4>
-__global__ void __launch_bounds__(64 * NW, NW / 2)
+template <int TW, int TH, int WM>
+__global__ void __launch_bounds__(256, 2)
 conv3x3_tiled_kernel(ConvArgs a)
 {
-    conv3x3_tiled_body<TW, TH, WM, VAR, NW>(a, blockIdx.x, gridDim.x);
+    conv3x3_tiled_body<TW, TH, WM>(a, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -599,7 +630,7 @@ conv3x3_tiled_kernel(ConvArgs a)
 //   t 0 1 2: OE(q) one each | t 4: EE(q) two, t 5: one | t 6: OO(q+1) three | t 8: EO(q+1) three.
 // TW == 16: a 16-pixel MFMA fragment is one output row of the tile (one address register per image width, the rest immediates);
 // otherwise (40 x 2 tiles for the 40-wide level) fragments run on across rows and every fragment has its own address.
-template <int TW, int TH, int WM, int VAR = 0>
+template <int TW, int TH, int WM>
 __global__ void __launch_bounds__(256, 2)
 conv3x3s2_tiled_kernel(ConvArgs a)
 {
@@ -612,7 +643,7 @@ conv3x3s2_tiled_kernel(ConvArgs a)
     constexpr int MT = TW * TH / 16 / WM, NT = 8 / WN;
     static_assert(TW * TH % (16 * WM) == 0 && 4 % WM == 0, "unsupported tile");
     static_assert(NPA == 3, "the static halo schedule below issues three pieces per phase image");
-    static_assert(kRing * kBBytes + 3 * kABytes <= 80 * 1024, "two workgroups per CU");
+    static_assert(kRing * kBBytes + 3 * kABytes == kS2LdsBytes && kS2LdsBytes <= 80 * 1024, "what the launcher asks for; two workgroups per CU");
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     unsigned char *const bufB = lds, *const bufA = lds + kRing * kBBytes;
 
@@ -658,8 +689,6 @@ conv3x3s2_tiled_kernel(ConvArgs a)
     const int wm = wave / WN, wn = wave % WN;
     const int fcol = lane & 15, fk = lane >> 4;
     const int w_rd = ((wn * NT) * 16 + fcol) * 64 + ((fk ^ tiled_swz(fcol)) << 4);
-    typedef unsigned long long u64;
-    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
     const uint32_t lds_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)bufA;
     // lane's pixel in a phase image of width PWID: tile pixel tp = (wm * MT + m) * 16 + fcol at (tp / TW + dr, tp % TW + dc)
     uint32_t pxE[kRowFrag ? 1 : MT], pxO[kRowFrag ? 1 : MT];      // images TW / TW + 1 pixels wide
@@ -672,14 +701,7 @@ conv3x3s2_tiled_kernel(ConvArgs a)
     auto read_px1 = [&](auto m_tag, auto pw_tag, auto off_tag, uint32_t buf_off, bf16x8 (&pf)[MT]) {
         constexpr int PWID = decltype(pw_tag)::value, OFF = decltype(off_tag)::value, m = decltype(m_tag)::value;
         constexpr int imm = OFF + (kRowFrag ? m * PWID * kPitch : 0);
-        const uint32_t addr = (PWID == TW ? pxE[kRowFrag ? 0 : m] : pxO[kRowFrag ? 0 : m]) + buf_off;
-        u64 lo, hi;
-        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "i"(imm));
-        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "i"(imm + 32));
-        u64x2 v;
-        v[0] = lo;
-        v[1] = hi;
-        pf[m] = __builtin_bit_cast(bf16x8, v);
+        pf[m] = ds_read_b64_pair<imm>((PWID == TW ? pxE[kRowFrag ? 0 : m] : pxO[kRowFrag ? 0 : m]) + buf_off);
     };
     auto read_px = [&](auto pw_tag, auto off_tag, uint32_t buf_off, bf16x8 (&pf)[MT]) {
         og_static_for<MT>([&](auto m_tag) { read_px1(m_tag, pw_tag, off_tag, buf_off, pf); });
@@ -768,11 +790,10 @@ conv3x3s2_tiled_kernel(ConvArgs a)
             const unsigned char *wB = bufB + (t % kRing) * kBBytes;
             // (the stride-1 kernel's interleaved issue -- DMA and fragment reads between the MFMAs -- was tried here too: -1 % alone, +0.35 %
             // in the network over five repeats, profiles/r05_c1_interleave_ab.log: not kept)
-            if (!(VAR & 2)) issue_dma();
             og_static_for<MT>([&](auto m_tag) { px_next(m_tag); });
 #pragma unroll
             for (int n = 0; n < NT; ++n) wf[n] = *reinterpret_cast<const bf16x8 *>(wB + w_rd + n * 1024);
-            if (VAR & 2) issue_dma();
+            issue_dma();       // behind the fragment reads: measured 1-4 % faster than in front of them
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int n = 0; n < NT; ++n)
@@ -926,11 +947,7 @@ conv1x1_tiled_kernel(PwArgs a)
         constexpr int HALF = decltype(half_tag)::value;
         const bool second = s >= steps1;
         const uint32_t soff = (uint32_t)((second ? s - steps1 : s) * 128);
-#if defined(OG_PW_ABL) && (OG_PW_ABL & 2)
-        const uint32_t beyond = kOobOffset;            // timing ablation (wrong results): no pixel traffic
-#else
         const uint32_t beyond = s >= steps ? kOobOffset : 0u;
-#endif
         const rsrc_t r = second ? x2r : x1r;
         og_static_for<MT>([&](auto m_tag) {
             constexpr int m = decltype(m_tag)::value;
@@ -943,11 +960,7 @@ conv1x1_tiled_kernel(PwArgs a)
     const uint32_t w_voff = (uint32_t)tid * 16;
     const uint32_t w_tile = (uint32_t)nt_i * (uint32_t)((a.C1 + a.C2) / 32 * kHalf);
     auto issue_b = [&](int s, int ring) {
-#if defined(OG_PW_ABL) && (OG_PW_ABL & 4)
-        const uint32_t voff = kOobOffset;              // timing ablation (wrong results): no weight traffic
-#else
         const uint32_t voff = w_voff | (s >= steps ? kOobOffset : 0u);
-#endif
 #pragma unroll
         for (int i = 0; i < PW; ++i)
             blds16(wr, voff, w_tile + s * kStage + i * 4096, lds + ring * kStage + piece + i * 4096);
@@ -1055,11 +1068,7 @@ conv1x1_tiled_kernel(PwArgs a)
 #pragma unroll 4
         for (int g = tid; g < 256 * kPerPx; g += 256) {
             const int px = g / kPerPx, cg = g % kPerPx, p = m0 + px;
-#if defined(OG_PW_ABL) && (OG_PW_ABL & 1)
-            if (p < a.M && cg == 1000)      // timing ablation (wrong results): no stores
-#else
             if (p < a.M)
-#endif
                 *reinterpret_cast<u16x8 *>(a.out + (size_t)p * a.Cout + n0 + cg * 8) = *reinterpret_cast<const u16x8 *>(lds + px * kOPitch + cg * 16);
         }
     } else {
@@ -1087,36 +1096,4 @@ conv1x1_tiled_kernel(PwArgs a)
     PW_STAMP(5);
     }      // work items
 #undef PW_STAMP
-}
-
-// Tile shape for (H, W): 1 = 16 x 16 (H, W multiples of 16), 2 = 40 x 4 (W == 40, H % 4 == 0), 3 = 20 x 4 (W == 20, H % 4 == 0),
-// 0 = none.
-static int tiled_kind(int H, int W, int Cin, int Cout)
-{
-    if (Cout % 128 || Cin % 64) return 0;
-    return (H % 16 == 0 && W % 16 == 0) ? 1 : (W == 40 && H % 4 == 0) ? 2 : (W == 20 && H % 4 == 0) ? 3 : 0;
-}
-
-// K slices for a level with few output tiles (< 200 workgroups against the chip's 512 slots), from the measurements of
-// profiles/r03_ksplit.log (batch 8, us per layer, 1 / 2 / 3 slices):
-//   40x40 384->256 (160 tiles of 40x4):  37.8 / 37.6 / 33.4    -> 3 slices where the chunks divide by 6
-//   40x40 256->256 (160 tiles, 8 chunks): 27.4 / 30.5 / --      -> no split (320 workgroups do not pay for 80 KiB slabs)
-//   40x40 384->384 (240 tiles):           43.5 / 43.9 / 51.7    -> no split: that level moves 7.8 KB of LDS-DMA per MFLOP
-//                                                                  and sits at the ~7 TB/s the L2 -> LDS path delivers either way
-//   20x20 384->384 (120 tiles of 20x4):   25.0 / 20.0 / 20.4    -> 2 slices (the split-K GEMM kernel: 21.6)
-// A slice always has an even number of chunks.
-static int tiled_ksplit(int kind, long items, int Cin)
-{
-    const int chunks = Cin / 32;
-    if (items >= 200) return 1;
-    if (kind == 3) return chunks % 4 == 0 ? 2 : 1;
-    if (kind == 2) return chunks % 6 == 0 ? 3 : 1;
-    return 1;
-}
-
-static size_t tiled_slab_bytes(int kind) { return (size_t)(kind == 1 ? 256 : kind == 2 ? 160 : 80) * 128 * 4; }
-static long tiled_items(int kind, int N, int H, int W, int Cout)
-{
-    const int tw = kind == 1 ? 16 : kind == 2 ? 40 : 20, th = kind == 1 ? 16 : 4;
-    return (long)N * (H / th) * (W / tw) * (Cout / 128);
 }
