@@ -91,10 +91,17 @@ def _f32_sum(v):
     return np.float32(np.sum(np.asarray(v, np.float32)))
 
 
-def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, use_scale=False, sort_dim=2):
-    """(L,k,13) limbs of one image -> (M,n_kp,6) poses (the per-row 'last matching column' form)."""
+def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, use_scale=False, sort_dim=2, trace=None):
+    """(L,k,13) limbs of one image -> (M,n_kp,6) poses (the per-row 'last matching column' form).
+
+    `trace`: a list that receives one record per limb type -- dict(l, kk, m0, anyA, anyB, multi_b = [(row, matching columns)] of the
+    rows that phase B meets with more than one column, pairs = the merge pairs (a, b), deleted = the rows the merges remove,
+    new_cols = the columns that start rows, M = live rows and P = rows ever created after the limb type) -- and a last one for
+    _delete_sort: dict(scores (float64, table order), kept (bool), npos = positive entries of the sort column per row, order = the
+    table rows in output order, hist = per table row the limb types that created or changed it)."""
     limbs = np.asarray(limbs, np.float32)
     rows = []                                                     # each: float32 (n_kp, 6), -1 = unset
+    hist, n_created = [], 0                                       # (trace) per live row: the limb types that touched it
     for l, (jf, jt) in enumerate(skeleton):
         cand = limbs[l]
         limit = np.maximum(np.float32(dist_max), cand[:, 12]) if use_scale else np.float32(dist_max)
@@ -104,6 +111,9 @@ def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, u
         _, first = np.unique(cand[:, 7].astype(np.int64), return_index=True)
         cand = cand[np.sort(first)]
         kk, mm = len(cand), len(rows)
+        rec = dict(l=l, kk=kk, m0=mm, anyA=False, anyB=False, multi_b=[], pairs=[], deleted=[], new_cols=[], M=mm, P=n_created)
+        if trace is not None:
+            trace.append(rec)
         if kk == 0:
             continue
         i1, i2, sc = cand[:, 6].astype(np.int64), cand[:, 7].astype(np.int64), cand[:, 10]
@@ -115,14 +125,19 @@ def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, u
             both = (hit == 2) & better
             if both.any():                                        # phase A: limb already known, keep the better score
                 pre = sub.copy()
+                rec['anyA'] = True
                 for m_, c_ in zip(*np.nonzero(both)):
+                    hist[m_].append(l)
                     sub[m_, jf, 4] = max(sc[c_], pre[m_, jf, 4])
                     sub[m_, jt, 4] = max(sc[c_], pre[m_, jt, 4])
                 hit[hit == 2] = -1
             one = (hit == 1) & better
             if one.any():                                         # phase B: extend a skeleton by the new joint
                 pre = sub.copy()
+                rec['anyB'] = True
+                rec['multi_b'] = [(int(m_), np.nonzero(one[m_])[0].tolist()) for m_ in np.nonzero(one.sum(1) > 1)[0]]
                 for m_, c_ in zip(*np.nonzero(one)):              # row-major: the last column wins per row
+                    hist[m_].append(l)
                     sub[m_, jf, 5], sub[m_, jt, 5] = cand[c_, 6], cand[c_, 7]
                     sub[m_, jf, 0:3], sub[m_, jf, 3] = cand[c_, 0:3], cand[c_, 11]
                     sub[m_, jt, 0:3], sub[m_, jt, 3] = cand[c_, 3:6], cand[c_, 12]
@@ -133,13 +148,16 @@ def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, u
             if mm >= 2:                                           # phase C: two skeletons sharing exactly two joints merge
                 ids = sub[:, :, 5].astype(np.int64)
                 pre = sub.copy()
-                for a in range(mm):
-                    for b in range(a + 1, mm):
-                        if int(((ids[a] == ids[b]) & (ids[a] != -1)).sum()) == 2:
-                            sub[a] = np.maximum(pre[a], pre[b])
-                            gone.add(b)
+                shared = ((ids[:, None, :] == ids[None, :, :]) & (ids[:, None, :] != -1)).sum(-1)
+                for a, b in zip(*np.nonzero(np.triu(shared == 2, 1))):      # row-major: the last partner wins per row
+                    sub[a] = np.maximum(pre[a], pre[b])
+                    gone.add(int(b))
+                    rec['pairs'].append((int(a), int(b)))
+                    hist[a].append(l)
             orphan = hit.sum(0) == 0
             rows = [sub[m_] for m_ in range(mm) if m_ not in gone]
+            hist = [hist[m_] for m_ in range(mm) if m_ not in gone]
+            rec['deleted'] = sorted(gone)
         else:
             orphan = np.ones(kk, bool)
         for c_ in np.nonzero(orphan)[0]:                          # phase D: unmatched limbs start new skeletons
@@ -147,13 +165,23 @@ def group_skeletons(limbs, skeleton, n_kp=17, person_thre=0.04, dist_max=40.0, u
             r[jf, 0:3], r[jf, 3], r[jf, 4], r[jf, 5] = cand[c_, 0:3], cand[c_, 11], sc[c_], cand[c_, 6]
             r[jt, 0:3], r[jt, 3], r[jt, 4], r[jt, 5] = cand[c_, 3:6], cand[c_, 12], sc[c_], cand[c_, 7]
             rows.append(r)
-    scored = []
-    for r in rows:
+            hist.append([l])
+            rec['new_cols'].append(int(c_))
+        n_created += len(rec['new_cols'])
+        rec['M'], rec['P'] = len(rows), n_created
+    scored, means, src = [], [], []
+    for m_, r in enumerate(rows):
         vals = r[:, sort_dim][r[:, sort_dim] > 0]
         mean = np.float64(_f32_sum(vals)) / np.float64(len(vals)) if len(vals) else np.float64('nan')
+        means.append(mean)
         if not mean < person_thre:
             scored.append((mean, r))
+            src.append(m_)
     order = sorted(range(len(scored)), key=lambda i: scored[i][0], reverse=True)   # stable
+    if trace is not None:
+        trace.append(dict(scores=np.array(means, np.float64), kept=np.array([not m_ < person_thre for m_ in means], bool),
+                          order=[src[i] for i in order], hist=hist,
+                          npos=np.array([int((r[:, sort_dim] > 0).sum()) for r in rows], np.int64)))
     out = np.stack([scored[i][1] for i in order]) if scored else np.zeros((0, n_kp, 6), np.float32)
     out[out == -1] = 0
     return out.astype(np.float32)
