@@ -743,6 +743,65 @@ typedef struct OgCocoMaskDesc {
 size_t og_coco_mask_workspace_bytes(const OgCocoMaskDesc *desc);
 int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- training step without a host wait (train_dist.py:304-342: the loss.item() batch drop, apex FusedAdam / torch SGD, and
+ * torch.nn.utils.clip_grad_norm_; offsetguided_amd.optim.DeviceAdam / DeviceSGD; csrc/optim.hip) ----  A multi-tensor optimizer that
+ * reads a device-side gradient scale: the scale carries the clip coefficient and the batch drop, so no step asks the host anything.
+ * Tensor table (device memory): `rows` int64[n_rows][5], one row (p, g, m, v, numel) per parameter that has a gradient -- four device
+ * addresses of dense fp32 data in one common element order (4-byte aligned, any offset beyond that) and the element count; m is the
+ * first moment (Adam) or the momentum buffer (SGD, unused with mom == 0), v the second moment (Adam only).  `chunk_prefix`
+ * int32[n_rows + 1] is the running sum of the rows' chunk counts, ceil(numel / og_optim_chunk_elems()), from 0 to the total: workgroup
+ * c finds its row by bisection and owns elements (c - chunk_prefix[row]) chunk .. + chunk of it.  A chunk whose offset leaves its row
+ * does nothing.  Inside a chunk: 16-byte loads and stores where the address allows (per tensor), scalar head and tail elsewhere.
+ * Workspace: a state block [scale f32, norm f32, dropped i32, 4 bytes unused] followed by one double per chunk; 8-byte aligned,
+ * og_optim_workspace_bytes(n_chunks) bytes (host arithmetic), owned by the caller across steps (`dropped` accumulates: zero it once).
+ * og_grad_sumsq_f32: every gradient element is squared and accumulated in double (an fp32 square is exact in double); partial c =
+ * the sum over chunk c in a fixed order (per thread in address order, lanes by a shuffle tree, waves in index order).  No atomics.
+ * og_step_scale_f32: ONE workgroup adds the partials in a fixed order (thread t its contiguous share in index order, the thread sums
+ * in index order) to n2 and writes the state block:
+ *     norm = (float)sqrt(n2)
+ *     drop = (loss != NULL && *loss > loss_limit) || !isfinite(n2)
+ *     drop:             scale = 0, dropped += 1
+ *     finite max_norm:  c = max_norm / (norm + 1e-6f) (fp32);  scale = c < 1 ? c : 1        (torch.nn.utils.clip_grad_norm_)
+ *     otherwise:        scale = 1
+ * `loss`: device pointer to the weighted fp32 loss, or NULL.  DELIBERATE DIFFERENCE from torch: a non-finite norm (an inf or NaN
+ * gradient anywhere) counts as a dropped batch; clip_grad_norm_ would multiply every gradient by NaN and poison every parameter.
+ * Updates: ONE launch over chunks chunk_first .. chunk_first + n_chunks of the table (a parameter group, or the parameters of one
+ * step count, is a run of rows); scalars by value, computed by the host in double and rounded to fp32 once; `state` = the workspace
+ * (scale is read from it) or NULL (scale = 1).  Every line is ONE individually rounded fp32 operation (-ffp-contract=off, correctly
+ * rounded divide and sqrt), per element:
+ *     ge = (scale == 0) ? 0 : g * scale          -- a dropped batch contributes exactly zero, even where g is inf / NaN
+ * og_adam_step_f32 (omb1 = 1 - b1, omb2 = 1 - b2, bc1 = 1 - b1^t, bc2 = 1 - b2^t; adam_w_mode 1 = apex FusedAdam's default, the
+ * reference's update; 0 = torch.optim.Adam's L2 form; identical with wd == 0):
+ *     if wd != 0 and not adam_w_mode:  t = wd * p;  ge = ge + t
+ *     a = b1 * m;   b = omb1 * ge;   m' = a + b
+ *     c = b2 * v;   d = omb2 * ge;   e = d * ge;   v' = c + e
+ *     mh = m' / bc1
+ *     q = v' / bc2;  r = sqrt(q);  den = r + eps
+ *     u = mh / den
+ *     if wd != 0 and adam_w_mode:      t = wd * p;  u = u + t
+ *     s = lr * u;   p' = p - s
+ * og_sgd_step_f32 (torch.optim.SGD, dampening 0, no Nesterov):
+ *     if wd != 0:  t = wd * p;  ge = ge + t
+ *     mom != 0, first:      buf = ge
+ *     mom != 0, not first:  t = mom * buf;  buf = t + ge
+ *     mom == 0:             buf stands for ge; no buffer is read or written
+ *     s = lr * buf;   p' = p - s
+ * All: no allocation, no synchronisation, graph-capturable; n_chunks == 0 launches nothing (og_step_scale_f32 always launches).
+ * OG_EINVAL (nothing launched): a null or misaligned table, workspace, loss or state; n_rows <= 0; a negative chunk count; a NaN
+ * max_norm or loss_limit; bc1 or bc2 not positive.  OG_ENOSPC: workspace_bytes too small.  The table's contents are device memory
+ * and are not validated: its builder answers for addresses and counts. */
+int og_optim_chunk_elems(void);
+size_t og_optim_workspace_bytes(int n_chunks);
+int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int og_step_scale_f32(int n_chunks, const float *loss, float loss_limit, float max_norm, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                     float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1, float bc2, int adam_w_mode,
+                     void *stream);
+int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                    float lr, float mom, float wd, int first, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,12 @@ SIGNATURES = {
     "og_oks_match_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "og_coco_mask_workspace_bytes": (_sz, [C.POINTER(CocoMaskDesc)]),
     "og_coco_masks_u8": (_i, [C.POINTER(CocoMaskDesc), _vp, _sz, _vp]),
+    "og_optim_chunk_elems": (_i, []),
+    "og_optim_workspace_bytes": (_sz, [_i]),
+    "og_grad_sumsq_f32": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "og_step_scale_f32": (_i, [_i, _vp, _f, _f, _vp, _sz, _vp]),
+    "og_adam_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp]),
+    "og_sgd_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

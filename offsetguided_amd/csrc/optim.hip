@@ -1,0 +1,394 @@
+// Multi-tensor optimizer step without a host wait (include/og_decoder.h, "training step"): the sum of squares of every gradient,
+// the device-side gradient scale (clip coefficient and batch drop in one number) and the Adam / SGD update, each ONE launch over a
+// table of tensors.  Memory-bound streaming kernels: one workgroup of 256 threads per chunk of OPTIM_CHUNK elements of one tensor,
+// 16-byte loads and stores wherever a tensor's address allows them, a scalar head and tail where it does not.  The arithmetic is the
+// header's list of individually rounded fp32 operations (the library is built with -ffp-contract=off, correctly rounded divide and
+// sqrt): tests/optim_common.py restates it in numpy and the GPU tests compare bit for bit.  No float atomics anywhere: the sum of
+// squares goes through per-chunk partials in double and a fixed-order reduction.
+#include "og_common.h"
+
+namespace {
+
+constexpr int OPTIM_THREADS = 256;
+constexpr int OPTIM_CHUNK = 8192;            // elements of one tensor per workgroup: 8 float4 per thread
+constexpr int OPTIM_STATE_BYTES = 16;        // [scale f32, norm f32, dropped i32, pad]; the double partials follow
+constexpr int SCALE_THREADS = 1024;
+
+// The table holds addresses as integers: the pointers made from them are given the global address space, so the loads and stores
+// are global_* instructions and not flat_* ones (a generic pointer would be checked against the LDS and scratch apertures).
+typedef __attribute__((address_space(1))) float gfloat;
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) f4 gf4;
+
+struct Row {
+    gfloat *p;
+    const gfloat *g;
+    gfloat *m;
+    gfloat *v;
+    long n;
+};
+
+struct Span {          // what a workgroup owns: elements [lo, hi) of its row, vectors of four from vs, n_vec of them, then the tail
+    long lo, hi, vs, tail;
+    int n_vec;
+};
+
+// Row of chunk `chunk`: the largest r < n_rows with prefix[r] <= chunk (prefix[n_rows] is the total).
+__device__ __forceinline__ int find_row(const int32_t *prefix, int n_rows, int chunk)
+{
+    int lo = 0, hi = n_rows;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= chunk) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// false: nothing to do (an offset at or past the row's end -- a table that does not match its prefix)
+__device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefix, int n_rows, int chunk, Row &row, Span &s)
+{
+    const int r = find_row(prefix, n_rows, chunk);
+    const int64_t *e = rows + (size_t)r * 5;
+    row.p = (gfloat *)(uintptr_t)e[0];
+    row.g = (const gfloat *)(uintptr_t)e[1];
+    row.m = (gfloat *)(uintptr_t)e[2];
+    row.v = (gfloat *)(uintptr_t)e[3];
+    row.n = e[4];
+    s.lo = (long)(chunk - prefix[r]) * OPTIM_CHUNK;
+    if (s.lo < 0 || s.lo >= row.n) return false;
+    s.hi = row.n - s.lo > OPTIM_CHUNK ? s.lo + OPTIM_CHUNK : row.n;
+    return true;
+}
+
+// The vector frame of a span is anchored on `anchor` (p for the updates, g for the sum of squares): lo is a multiple of four
+// elements, so the first 16-byte aligned element of every chunk sits `head` elements in.
+__device__ __forceinline__ void frame(const gfloat *anchor, Span &s)
+{
+    const int head = (int)(((16u - (unsigned)((uintptr_t)anchor & 15u)) & 15u) >> 2);
+    s.vs = s.lo + head < s.hi ? s.lo + head : s.hi;
+    s.n_vec = (int)((s.hi - s.vs) >> 2);
+    s.tail = s.vs + 4L * s.n_vec;
+}
+
+__device__ __forceinline__ bool aligned16(const gfloat *q) { return ((uintptr_t)q & 15u) == 0; }
+
+__device__ __forceinline__ f4 load4(const gfloat *q, bool vec)
+{
+    if (vec) return *(const gf4 *)q;
+    f4 x;
+    x.x = q[0];
+    x.y = q[1];
+    x.z = q[2];
+    x.w = q[3];
+    return x;
+}
+
+__device__ __forceinline__ void store4(gfloat *q, bool vec, f4 x)
+{
+    if (vec) {
+        *(gf4 *)q = x;
+    } else {
+        q[0] = x.x;
+        q[1] = x.y;
+        q[2] = x.z;
+        q[3] = x.w;
+    }
+}
+
+// The scalar elements of a span, one thread each: the head on threads 0.., the tail on threads 64.. (another wave).  -1: none.
+__device__ __forceinline__ long edge_element(const Span &s)
+{
+    const int t = threadIdx.x;
+    if (t < (int)(s.vs - s.lo)) return s.lo + t;
+    if (t >= 64 && t - 64 < (int)(s.hi - s.tail)) return s.tail + (t - 64);
+    return -1;
+}
+
+// ---- sum of squares ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OPTIM_THREADS) void grad_sumsq_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
+                                                                   int n_rows, double *__restrict__ partials)
+{
+    __shared__ double wave_sum[OPTIM_THREADS / 64];
+    Row row;
+    Span s;
+    double acc = 0.0;
+    if (locate(rows, prefix, n_rows, blockIdx.x, row, s)) {
+        frame(row.g + s.lo, s);
+        for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+            const f4 g = *(const gf4 *)(row.g + s.vs + 4L * k);
+            acc += (double)g.x * (double)g.x;
+            acc += (double)g.y * (double)g.y;
+            acc += (double)g.z * (double)g.z;
+            acc += (double)g.w * (double)g.w;
+        }
+        const long e = edge_element(s);
+        if (e >= 0) {
+            const double g = (double)row.g[e];
+            acc += g * g;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// ---- the scale block -----------------------------------------------------------------------------------------------------------
+// One workgroup.  Thread t sums its contiguous share of the partials in index order; the 1024 thread sums are added in index order
+// sixteen at a time by wave 0, whose lanes are folded by a shuffle tree: one fixed order for a given number of partials.
+__global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double *__restrict__ partials, int n_partials,
+                                                                   const float *__restrict__ loss, float loss_limit, float max_norm,
+                                                                   float *__restrict__ state)
+{
+    __shared__ double sums[SCALE_THREADS];
+    const int per = (n_partials + SCALE_THREADS - 1) / SCALE_THREADS;
+    const int first = threadIdx.x * per;
+    const int last = first + per < n_partials ? first + per : n_partials;
+    double acc = 0.0;
+    for (int i = first; i < last; ++i) acc += partials[i];
+    sums[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        double a = 0.0;
+        for (int i = 0; i < SCALE_THREADS / 64; ++i) a += sums[threadIdx.x * (SCALE_THREADS / 64) + i];
+        for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+        if (threadIdx.x == 0) {
+            const double n2 = a;
+            const float norm = (float)sqrt(n2);
+            const bool drop = (loss != nullptr && *loss > loss_limit) || !isfinite(n2);
+            float scale = 1.f;
+            if (drop) {
+                scale = 0.f;
+            } else if (isfinite(max_norm)) {
+                const float den = norm + 1e-6f;
+                const float c = max_norm / den;
+                scale = c < 1.f ? c : 1.f;
+            }
+            state[0] = scale;
+            state[1] = norm;
+            if (drop) reinterpret_cast<int *>(state)[2] += 1;
+        }
+    }
+}
+
+// ---- updates -------------------------------------------------------------------------------------------------------------------
+struct AdamArgs {
+    float lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2;
+    int adam_w_mode;
+};
+
+__device__ __forceinline__ void adam_element(const AdamArgs &a, float scale, float &p, float g, float &m, float &v)
+{
+    float ge = (scale == 0.f) ? 0.f : g * scale;
+    if (a.wd != 0.f && !a.adam_w_mode) {
+        const float t = a.wd * p;
+        ge = ge + t;
+    }
+    const float x = a.b1 * m;
+    const float y = a.omb1 * ge;
+    m = x + y;
+    const float c = a.b2 * v;
+    const float d = a.omb2 * ge;
+    const float e = d * ge;
+    v = c + e;
+    const float mh = m / a.bc1;
+    const float q = v / a.bc2;
+    const float r = sqrtf(q);
+    const float den = r + a.eps;
+    float u = mh / den;
+    if (a.wd != 0.f && a.adam_w_mode) {
+        const float t = a.wd * p;
+        u = u + t;
+    }
+    const float s = a.lr * u;
+    p = p - s;
+}
+
+__global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
+                                                                  int n_rows, int chunk_first, const float *__restrict__ state, AdamArgs a)
+{
+    Row row;
+    Span s;
+    if (!locate(rows, prefix, n_rows, chunk_first + blockIdx.x, row, s)) return;
+    const float scale = state ? state[0] : 1.f;
+    frame(row.p + s.lo, s);
+    const bool gv = aligned16(row.g + s.vs), mv = aligned16(row.m + s.vs), vv = aligned16(row.v + s.vs);
+#pragma unroll 2
+    for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+        const long i = s.vs + 4L * k;
+        f4 p = *(const gf4 *)(row.p + i);
+        const f4 g = load4(row.g + i, gv);
+        f4 m = load4(row.m + i, mv);
+        f4 v = load4(row.v + i, vv);
+#define ADAM_LANE(c)                                  \
+    {                                                 \
+        float p_ = p.c, m_ = m.c, v_ = v.c;           \
+        adam_element(a, scale, p_, g.c, m_, v_);      \
+        p.c = p_, m.c = m_, v.c = v_;                 \
+    }
+        ADAM_LANE(x) ADAM_LANE(y) ADAM_LANE(z) ADAM_LANE(w)
+#undef ADAM_LANE
+        *(gf4 *)(row.p + i) = p;
+        store4(row.m + i, mv, m);
+        store4(row.v + i, vv, v);
+    }
+    const long e = edge_element(s);
+    if (e >= 0) {
+        float p = row.p[e], m = row.m[e], v = row.v[e];
+        adam_element(a, scale, p, row.g[e], m, v);
+        row.p[e] = p;
+        row.m[e] = m;
+        row.v[e] = v;
+    }
+}
+
+struct SgdArgs {
+    float lr, mom, wd;
+    int first;
+};
+
+// buf is read only when HAS_BUF && !first, written only when HAS_BUF
+template <bool HAS_BUF>
+__device__ __forceinline__ void sgd_element(const SgdArgs &a, float scale, float &p, float g, float &buf)
+{
+    float ge = (scale == 0.f) ? 0.f : g * scale;
+    if (a.wd != 0.f) {
+        const float t = a.wd * p;
+        ge = ge + t;
+    }
+    float step = ge;
+    if (HAS_BUF) {
+        if (!a.first) {
+            const float t = a.mom * buf;
+            step = t + ge;
+        }
+        buf = step;
+    }
+    const float s = a.lr * step;
+    p = p - s;
+}
+
+template <bool HAS_BUF>
+__global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
+                                                                 int n_rows, int chunk_first, const float *__restrict__ state, SgdArgs a)
+{
+    Row row;
+    Span s;
+    if (!locate(rows, prefix, n_rows, chunk_first + blockIdx.x, row, s)) return;
+    const float scale = state ? state[0] : 1.f;
+    frame(row.p + s.lo, s);
+    const bool gv = aligned16(row.g + s.vs), mv = HAS_BUF && aligned16(row.m + s.vs);
+    const bool read_buf = HAS_BUF && !a.first;
+#pragma unroll 2
+    for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+        const long i = s.vs + 4L * k;
+        f4 p = *(const gf4 *)(row.p + i);
+        const f4 g = load4(row.g + i, gv);
+        f4 m = {0.f, 0.f, 0.f, 0.f};
+        if (read_buf) m = load4(row.m + i, mv);
+#define SGD_LANE(c)                                       \
+    {                                                     \
+        float p_ = p.c, m_ = m.c;                         \
+        sgd_element<HAS_BUF>(a, scale, p_, g.c, m_);      \
+        p.c = p_, m.c = m_;                               \
+    }
+        SGD_LANE(x) SGD_LANE(y) SGD_LANE(z) SGD_LANE(w)
+#undef SGD_LANE
+        *(gf4 *)(row.p + i) = p;
+        if (HAS_BUF) store4(row.m + i, mv, m);
+    }
+    const long e = edge_element(s);
+    if (e >= 0) {
+        float p = row.p[e], m = read_buf ? row.m[e] : 0.f;
+        sgd_element<HAS_BUF>(a, scale, p, row.g[e], m);
+        row.p[e] = p;
+        if (HAS_BUF) row.m[e] = m;
+    }
+}
+
+int check_table(const char *name, const void *rows, const void *prefix, int n_rows, int chunk_first, int n_chunks)
+{
+    OG_REQUIRE(rows && prefix, OG_EINVAL, "%s: null table", name);
+    OG_REQUIRE(((uintptr_t)rows & 7u) == 0 && ((uintptr_t)prefix & 3u) == 0, OG_EINVAL, "%s: misaligned table", name);
+    OG_REQUIRE(n_rows > 0 && chunk_first >= 0 && n_chunks >= 0, OG_EINVAL, "%s: bad table size (%d rows, chunks %d + %d)", name, n_rows,
+               chunk_first, n_chunks);
+    return OG_OK;
+}
+
+}  // namespace
+
+OG_API int og_optim_chunk_elems(void) { return OPTIM_CHUNK; }
+
+OG_API size_t og_optim_workspace_bytes(int n_chunks)
+{
+    return n_chunks < 0 ? 0 : (size_t)OPTIM_STATE_BYTES + (size_t)n_chunks * sizeof(double);
+}
+
+OG_API int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, void *workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    const char *name = "og_grad_sumsq_f32";
+    if (int rc = check_table(name, rows, chunk_prefix, n_rows, 0, n_chunks)) return rc;
+    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
+    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
+               workspace_bytes, og_optim_workspace_bytes(n_chunks));
+    if (n_chunks == 0) return OG_OK;
+    double *partials = reinterpret_cast<double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                       partials);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
+OG_API int og_step_scale_f32(int n_chunks, const float *loss, float loss_limit, float max_norm, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    const char *name = "og_step_scale_f32";
+    OG_REQUIRE(n_chunks >= 0, OG_EINVAL, "%s: negative chunk count", name);
+    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
+    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
+               workspace_bytes, og_optim_workspace_bytes(n_chunks));
+    OG_REQUIRE(!(max_norm != max_norm) && !(loss_limit != loss_limit), OG_EINVAL, "%s: NaN max_norm or loss_limit", name);
+    OG_REQUIRE(((uintptr_t)loss & 3u) == 0, OG_EINVAL, "%s: misaligned loss", name);
+    float *state = static_cast<float *>(workspace);
+    const double *partials = reinterpret_cast<const double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
+    hipLaunchKernelGGL(step_scale_kernel, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss, loss_limit,
+                       max_norm, state);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
+OG_API int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks,
+                            const void *state, float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                            float bc2, int adam_w_mode, void *stream)
+{
+    const char *name = "og_adam_step_f32";
+    if (int rc = check_table(name, rows, chunk_prefix, n_rows, chunk_first, n_chunks)) return rc;
+    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
+    OG_REQUIRE(bc1 > 0.f && bc2 > 0.f, OG_EINVAL, "%s: bias corrections must be positive (bc1 %g, bc2 %g)", name, bc1, bc2);
+    if (n_chunks == 0) return OG_OK;
+    const AdamArgs a{lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, adam_w_mode != 0};
+    hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                       chunk_first, static_cast<const float *>(state), a);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
+OG_API int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                           float lr, float mom, float wd, int first, void *stream)
+{
+    const char *name = "og_sgd_step_f32";
+    if (int rc = check_table(name, rows, chunk_prefix, n_rows, chunk_first, n_chunks)) return rc;
+    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
+    if (n_chunks == 0) return OG_OK;
+    const SgdArgs a{lr, mom, wd, first != 0};
+    if (mom != 0.f)
+        hipLaunchKernelGGL(sgd_step_kernel<true>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                           chunk_first, static_cast<const float *>(state), a);
+    else
+        hipLaunchKernelGGL(sgd_step_kernel<false>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                           chunk_first, static_cast<const float *>(state), a);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}

@@ -1,0 +1,293 @@
+"""Optimizers whose step never waits for the device: DeviceAdam (apex FusedAdam of the reference, train_dist.py:236-246) and
+DeviceSGD on the multi-tensor HIP kernels of csrc/optim.hip (include/og_decoder.h, "training step without a host wait").
+
+step(loss=..., max_grad_norm=...) queues three launches on the current stream: the sum of squares of every gradient, the scale block
+(the clip coefficient of torch.nn.utils.clip_grad_norm_ and the reference's `loss > 1e8` batch drop in ONE device-side number), and
+the update, which multiplies every gradient by that number.  Nothing is read back: `last_grad_norm` and `dropped_steps` are device
+tensors the caller converts when it prints.
+
+The state keys are torch's (`step`, `exp_avg`, `exp_avg_sq`, `momentum_buffer`): a checkpoint written with torch.optim.Adam / SGD
+resumes here and the other way round.  `step` is counted on the host; the tensors under state[p]['step'] are brought up to date by
+state_dict().
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _same_layout(a, b):
+    """Same element order in memory: equal strides on every dimension longer than one."""
+    return a.shape == b.shape and all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n != 1)
+
+
+def _dense(t):
+    """Non-overlapping and dense: the tensor's elements are numel() consecutive addresses in some order."""
+    if t.is_contiguous():
+        return True
+    expected = 1
+    for stride, size in sorted((st, n) for n, st in zip(t.shape, t.stride()) if n != 1):
+        if stride != expected:
+            return False
+        expected *= size
+    return True
+
+
+class _TableSlot:
+    """One pinned staging area of the tensor table; `event` is recorded behind the copy that reads it."""
+
+    def __init__(self, nbytes):
+        self.buf = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
+        self.event = None
+
+    def free(self):
+        return self.event is None or self.event.query()
+
+
+class _DeviceOptimizer(torch.optim.Optimizer):
+    MOMENTS = ()      # state keys of the m and v columns of the table
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._steps = {}          # parameter -> steps taken (the host's count; state[p]['step'] follows in state_dict())
+        self._checked = set()     # parameters whose state tensors are known to have the parameter's layout
+        self._signature = None    # what the device table was built from
+        self._table = None
+        self._segments = []       # (group index, key, first chunk, chunk count)
+        self._n_rows = self._n_chunks = 0
+        self._slots = []
+        self._ws = None
+
+    # ---- the state block ------------------------------------------------------------------------------------------------------
+    def _device(self):
+        for group in self.param_groups:
+            for p in group['params']:
+                if not p.is_cuda:
+                    raise _lib.OgError(f'{type(self).__name__}: parameter on {p.device}; the HIP optimizer kernels need GPU tensors '
+                                       '(offsetguided_amd has no CPU path)')
+                return p.device
+        raise _lib.OgError(f'{type(self).__name__}: no parameters')
+
+    def _workspace(self, dev, lib):
+        chunk = lib.og_optim_chunk_elems()
+        most = sum(-(-p.numel() // chunk) for group in self.param_groups for p in group['params'])
+        need = lib.og_optim_workspace_bytes(most)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+            if self._ws is not None and self._ws.device == dev:
+                ws[:16].copy_(self._ws[:16])          # the dropped-batch count lives on
+            self._ws = ws
+        return self._ws
+
+    @property
+    def last_grad_norm(self):
+        """fp32 device scalar: the gradient norm of the last step that computed one (before clipping)."""
+        return self._workspace(self._device(), _lib.load())[4:8].view(torch.float32)[0]
+
+    @property
+    def last_scale(self):
+        """fp32 device scalar: what that step multiplied the gradients by (0: dropped, below 1: clipped)."""
+        return self._workspace(self._device(), _lib.load())[0:4].view(torch.float32)[0]
+
+    @property
+    def dropped_steps(self):
+        """int32 device scalar: steps dropped so far (loss above loss_limit, or a non-finite gradient)."""
+        return self._workspace(self._device(), _lib.load())[8:12].view(torch.int32)[0]
+
+    # ---- checkpoints ----------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        for p, t in self._steps.items():
+            if p in self.state:
+                self.state[p]['step'] = torch.tensor(float(t), dtype=torch.float32)
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        for group in state_dict['param_groups']:
+            if group.get('amsgrad') or group.get('maximize') or group.get('nesterov') or group.get('dampening'):
+                raise ValueError(f'{type(self).__name__}: the checkpoint asks for amsgrad, maximize, nesterov or dampening, which the '
+                                 'HIP kernels do not implement')
+        own = [dict(group) for group in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, old in zip(self.param_groups, own):     # a torch checkpoint has no adam_w_mode: this optimizer's stays
+            for k, v in old.items():
+                group.setdefault(k, v)
+        self._steps = {p: int(round(float(st['step']))) for p, st in self.state.items() if st.get('step') is not None}
+        self._checked = set()
+        self._signature = None
+
+    # ---- the tensor table -----------------------------------------------------------------------------------------------------
+    def _init_state(self, p, group, state):
+        raise NotImplementedError
+
+    def _key(self, p, group, state):
+        raise NotImplementedError
+
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+        raise NotImplementedError
+
+    def _after(self, entries):
+        pass
+
+    def _entries(self, dev):
+        """[(group index, segment key, parameter, gradient, state)] of the parameters that have a gradient, segment by segment."""
+        out = []
+        for gi, group in enumerate(self.param_groups):
+            for p in group['params']:
+                g = p.grad
+                if g is None:
+                    continue
+                if not p.is_cuda or not g.is_cuda:
+                    raise _lib.OgError(f'{type(self).__name__}.step: parameter on {p.device}; the HIP optimizer kernels need GPU '
+                                       'tensors (offsetguided_amd has no CPU path)')
+                if p.device != dev:
+                    raise _lib.OgError(f'{type(self).__name__}.step: parameters on {dev} and {p.device}; one device per optimizer')
+                if p.dtype != torch.float32 or g.dtype != torch.float32 or g.is_sparse:
+                    raise _lib.OgError(f'{type(self).__name__}.step: dense fp32 parameters and gradients only (got {p.dtype}, {g.dtype})')
+                if p.numel() == 0:
+                    continue
+                state = self.state[p]
+                if p not in self._checked:
+                    if not _dense(p):
+                        raise _lib.OgError(f'{type(self).__name__}.step: a parameter of shape {tuple(p.shape)} with strides '
+                                           f'{p.stride()} is not dense')
+                    self._init_state(p, group, state)
+                    for k in self.MOMENTS:          # a checkpoint of another memory format: bring it to the parameter's
+                        if state.get(k) is not None and not _same_layout(state[k], p):
+                            state[k] = torch.empty_like(p).copy_(state[k])
+                    self._checked.add(p)
+                if not _same_layout(g, p):
+                    g = torch.empty_like(p).copy_(g)
+                out.append((gi, self._key(p, group, state), p, g, state))
+        out.sort(key=lambda e: e[:2])               # stable: list order inside a segment
+        return out
+
+    def _upload(self, entries, dev, lib):
+        chunk = lib.og_optim_chunk_elems()
+        moments = self.MOMENTS + (None,) * (2 - len(self.MOMENTS))
+        rows = [(p.data_ptr(), g.data_ptr(), *(st[k].data_ptr() if k and st.get(k) is not None else 0 for k in moments), p.numel())
+                for _, _, p, g, st in entries]
+        keys = [e[:2] for e in entries]
+        signature = (rows, keys)
+        if signature == self._signature:
+            return
+        table = np.array(rows, dtype=np.int64).reshape(-1, 5)
+        prefix = np.zeros(len(rows) + 1, dtype=np.int32)
+        np.cumsum(-(-table[:, 4] // chunk), out=prefix[1:])
+        self._segments = []
+        for i, key in enumerate(keys):
+            if i == 0 or key != keys[i - 1]:
+                self._segments.append([key[0], key[1], int(prefix[i]), 0])
+            self._segments[-1][3] = int(prefix[i + 1]) - self._segments[-1][2]
+        raw = np.concatenate([table.reshape(-1).view(np.uint8), prefix.view(np.uint8)])
+        # pinned slots (decoder.factory._HostSlot): one is written again only after the copy that read it has finished
+        slot = next((s for s in self._slots if s.buf.numel() >= raw.size and s.free()), None)
+        if slot is None:
+            slot = _TableSlot(raw.size * 2)
+            self._slots.append(slot)
+        slot.buf[:raw.size].copy_(torch.from_numpy(raw))
+        self._table = torch.empty(raw.size, dtype=torch.uint8, device=dev)
+        self._table.copy_(slot.buf[:raw.size], non_blocking=True)
+        slot.event = torch.cuda.Event()
+        slot.event.record(torch.cuda.current_stream(dev))
+        self._n_rows, self._n_chunks = len(rows), int(prefix[-1])
+        self._signature = signature
+
+    @torch.no_grad()
+    def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8):
+        """Queue one optimisation step on the current stream.  loss: the weighted fp32 loss on the device (a batch whose loss exceeds
+        loss_limit is dropped); max_grad_norm: clip_grad_norm_'s max_norm over every gradient.  With neither, only the update runs.
+        Never waits for the device."""
+        out = None
+        if closure is not None:
+            with torch.enable_grad():
+                out = closure()
+        if max_grad_norm != max_grad_norm or max_grad_norm <= 0:
+            raise ValueError(f'max_grad_norm must be positive, got {max_grad_norm}')
+        dev = self._device()
+        lib = _lib.load()
+        entries = self._entries(dev)
+        if not entries:
+            return out
+        with torch.cuda.device(dev):
+            ws = self._workspace(dev, lib)
+            self._upload(entries, dev, lib)
+            stream = _lib.stream_ptr(dev)
+            rows, prefix = self._table.data_ptr(), self._table.data_ptr() + 40 * self._n_rows
+            state_ptr = None
+            if loss is not None or math.isfinite(max_grad_norm):
+                if loss is not None:
+                    loss = _lib.require_device(loss.detach(), 'loss')
+                    if loss.numel() != 1:
+                        raise ValueError(f'loss: one element expected, got {tuple(loss.shape)}')
+                _lib.check(lib.og_grad_sumsq_f32(rows, prefix, self._n_rows, self._n_chunks, _lib.ptr(ws), ws.numel(), stream), lib)
+                _lib.check(lib.og_step_scale_f32(self._n_chunks, _lib.ptr(loss) if loss is not None else None, loss_limit, max_grad_norm,
+                                                 _lib.ptr(ws), ws.numel(), stream), lib)
+                state_ptr = _lib.ptr(ws)
+            for gi, key, first, count in self._segments:
+                self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream)
+        self._after(entries)
+        return out
+
+
+class DeviceAdam(_DeviceOptimizer):
+    """Adam on og_adam_step_f32.  adam_w_mode=True (apex FusedAdam's default, the reference's update) decays the weights next to the
+    step; False is torch.optim.Adam's L2 form; with weight_decay == 0 the two are the same."""
+    MOMENTS = ('exp_avg', 'exp_avg_sq')
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, adam_w_mode=True):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError(f'DeviceAdam: bad hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}')
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, adam_w_mode=bool(adam_w_mode)))
+
+    def _init_state(self, p, group, state):
+        if 'exp_avg' not in state:
+            state['step'] = torch.tensor(0.0, dtype=torch.float32)
+            state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        self._steps.setdefault(p, 0)
+
+    def _key(self, p, group, state):
+        return self._steps[p]
+
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+        t = key + 1
+        b1, b2 = group['betas']
+        _lib.check(lib.og_adam_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], b1, b2, 1.0 - b1, 1.0 - b2,
+                                        group['eps'], group['weight_decay'], 1.0 - b1 ** t, 1.0 - b2 ** t,
+                                        int(group.get('adam_w_mode', True)), stream), lib)
+
+    def _after(self, entries):
+        for _, _, p, _, _ in entries:
+            self._steps[p] += 1
+
+
+class DeviceSGD(_DeviceOptimizer):
+    """torch.optim.SGD (dampening 0, no Nesterov) on og_sgd_step_f32; with momentum == 0 no buffer exists."""
+    MOMENTS = ('momentum_buffer',)
+
+    def __init__(self, params, lr, momentum=0, weight_decay=0):
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError(f'DeviceSGD: bad hyper-parameters lr={lr} momentum={momentum} weight_decay={weight_decay}')
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        self._fresh = set()       # parameters whose momentum buffer has not been written yet
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._fresh = set()
+
+    def _init_state(self, p, group, state):
+        if group['momentum'] != 0 and state.get('momentum_buffer') is None:
+            state['momentum_buffer'] = torch.zeros_like(p, memory_format=torch.preserve_format)    # the first step writes it, reads nothing
+            self._fresh.add(p)
+
+    def _key(self, p, group, state):
+        return 1 if p in self._fresh else 0
+
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+        _lib.check(lib.og_sgd_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], group['momentum'],
+                                       group['weight_decay'], key, stream), lib)
+
+    def _after(self, entries):
+        self._fresh.difference_update(e[2] for e in entries)

@@ -5,7 +5,8 @@
     (delay_allreduce=True: one flat            all-reduce overlaps the rest of backward (xGMI links are
      all-reduce after backward)                point-to-point, so overlap matters more than on NVSwitch)
   apex SyncBatchNorm                      -> torch.nn.SyncBatchNorm (optional, --no-sync-bn)
-  apex FusedAdam                          -> torch.optim.Adam(fused=True)
+  apex FusedAdam                          -> torch.optim.Adam(fused=True); --device-step: optim.DeviceAdam / DeviceSGD (csrc/optim.hip),
+    loss.item() batch drop (:322)             gradient clipping and the batch drop as one device-side scale: no host wait in the step
   mask/gather losses                      -> fused HIP loss kernels (models/losses.py, csrc/losses.hip)
 
 One process per GPU (`python -m torch.distributed.run --nproc-per-node N -m offsetguided_amd.train_dist`);
@@ -21,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, encoder, models, sharding, synth, transforms
+from . import _lib, encoder, models, optim, sharding, synth, transforms
 from .config import coco_data as cd
 from .utils import AverageMeter, adjust_learning_rate
 
@@ -30,6 +31,12 @@ def train_cli(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     models.net_cli(p)
     p.add_argument('--resume', '-r', action='store_true', default=False)
+    p.add_argument('--drop-optim-state', dest='resume_optimizer', action='store_false', default=True,
+                   help='do not resume the optimizer from the checkpoint')
+    p.add_argument('--drop-layers', action='store_true', default=False,
+                   help='drop the offset convolutions of the checkpoint (--resume, or a --checkpoint-whole start)')
+    p.add_argument('--recount-epoch', action='store_true', default=False, help='restart the epoch counter at 0 after --resume')
+    p.add_argument('--freeze', action='store_true', default=False, help='freeze the layers of the BaseNet, i.e. the backbone')
     p.add_argument('--epochs', default=100, type=int)
     p.add_argument('--warmup', action='store_true', default=False, help='warm-up learning rate')
     p.add_argument('--checkpoint-path', '-p', default='link2checkpoints_storage')
@@ -75,7 +82,16 @@ def train_cli(argv=None):
     g.add_argument('--learning-rate', type=float, default=2.5e-4, help='learning rate for world size 1')
     g.add_argument('--momentum', default=0.9, type=float)
     g.add_argument('--weight-decay', '--wd', default=0, type=float)
+    g.add_argument('--device-step', action='store_true', default=False,
+                   help='step with the HIP multi-tensor optimizer (optim.DeviceAdam / DeviceSGD): the exploding-batch drop and the '
+                        'gradient clipping are one device-side scale, losses stay on the device between --print-freq lines')
+    g.add_argument('--max-grad-norm', default=float('inf'), type=float,
+                   help='clip the norm of all gradients to this value, as torch.nn.utils.clip_grad_norm_ does (with --device-step)')
     args = p.parse_args(argv)
+    if args.max_grad_norm != float('inf') and not args.device_step:
+        p.error('--max-grad-norm is applied by the device-side step: add --device-step')
+    if not args.max_grad_norm > 0:
+        p.error('--max-grad-norm must be positive')
     if bool(args.train_annotations) != bool(args.train_image_dir):
         p.error('--train-annotations and --train-image-dir go together')
     if args.train_annotations:
@@ -216,6 +232,72 @@ def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dty
     return loss.detach(), [float(l.detach()) if torch.is_tensor(l) else float(l) for l in multi_losses]
 
 
+def train_step_device(model, criterion, optimizer, images, annos, lambdas, autocast_dtype=torch.bfloat16, max_grad_norm=float('inf'),
+                      world=1):
+    """train_step for optim.DeviceAdam / DeviceSGD: nothing is read back.  backward() runs on the real loss; the step multiplies the
+    gradients by the device-side scale -- 0 for a batch whose loss exceeds 1e8 (train_dist.py:322-325) or whose gradients are not
+    finite, the clip_grad_norm_ coefficient of --max-grad-norm otherwise.  Under DDP the gradients are all-reduced when backward()
+    returns, so every rank takes the same norm; the loss the drop looks at is the largest over the ranks, so every rank drops the same
+    batches.  Returns (loss, per-head losses) as device tensors."""
+    optimizer.zero_grad(set_to_none=True)
+    dev_type = 'cuda' if images.is_cuda else 'cpu'
+    with torch.autocast(dev_type, dtype=autocast_dtype, enabled=autocast_dtype is not None):
+        outputs = model(images)
+    multi_losses = []
+    for out, lossfun, anno in zip(outputs, criterion, annos):
+        out32 = tuple([o.float() if isinstance(o, torch.Tensor) else o for o in part] for part in out)
+        multi_losses += list(lossfun(out32, *anno))
+    assert len(multi_losses) <= len(lambdas), 'lambdas is incomplete'
+    loss = sum(lam * l for lam, l in zip(lambdas, multi_losses))
+    loss.backward()
+    loss = loss.detach()
+    guard = loss
+    if world > 1:
+        guard = loss.clone()
+        torch.distributed.all_reduce(guard, op=torch.distributed.ReduceOp.MAX)
+    optimizer.step(loss=guard, max_grad_norm=max_grad_norm)
+    return loss, [l.detach() if torch.is_tensor(l) else l for l in multi_losses]
+
+
+def freeze_backbone(model):
+    """--freeze (train_dist.py:202-206): the BaseNet's parameters take no gradient; call before the optimizer is made."""
+    for name, param in model.named_parameters():
+        if 'basenet' in name:
+            param.requires_grad = False
+    return model
+
+
+def make_optimizer(args, model, world, use_cuda):
+    """The optimizer of a run over the parameters that take a gradient (train_dist.py:208-222)."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    lr = args.learning_rate * world
+    if getattr(args, 'device_step', False):
+        if args.optimizer == 'adam':
+            return optim.DeviceAdam(params, lr=lr, weight_decay=args.weight_decay)
+        return optim.DeviceSGD(params, lr=lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    if args.optimizer == 'adam':
+        return torch.optim.Adam(params, lr=lr, weight_decay=args.weight_decay, fused=use_cuda)
+    return torch.optim.SGD(params, lr=lr, momentum=args.momentum, weight_decay=args.weight_decay)
+
+
+def load_checkpoint(args, model, optimizer, use_cuda):
+    """--resume (train_dist.py:230-236, :267-268): weights, optimizer state unless --drop-optim-state, and the epoch the LR schedule
+    is at unless --recount-epoch.  Without --resume, --checkpoint-whole initialises the weights only (fine-tuning, as
+    evaluate.py:189-191 loads it); a path that does not exist is an error (load_model raises FileNotFoundError), never a silent
+    random init.  -> (model, optimizer, start_epoch, start_loss or None)."""
+    drop_layers = getattr(args, 'drop_layers', False)
+    if args.resume:
+        if not args.checkpoint_whole:
+            raise ValueError('--resume needs --checkpoint-whole <file>')
+        model, optimizer, start_epoch, start_loss, _ = models.load_model(
+            model, args.checkpoint_whole, optimizer=optimizer, resume_optimizer=getattr(args, 'resume_optimizer', True),
+            drop_layers=drop_layers, optimizer2cuda=use_cuda)
+        return model, optimizer, 0 if getattr(args, 'recount_epoch', False) else start_epoch, start_loss
+    if args.checkpoint_whole:
+        model, *_ = models.load_model(model, args.checkpoint_whole, optimizer=None, resume_optimizer=False, drop_layers=drop_layers)
+    return model, optimizer, 0, None
+
+
 def describe_losses(args):
     """The heads and loss choices of a run, for the --bench line: the default is 'focal-L2 hmp + L1 offset losses'."""
     short = lambda name: {'focal_l2_loss': 'focal-L2', 'l2_loss': 'L2', 'offset_l1_loss': 'L1', 'vector_l1_loss': 'vector-L1',  # noqa: E731
@@ -243,6 +325,7 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
     dist = torch.distributed
 
     augment_events = []
+    device_step = getattr(args, 'device_step', False)
 
     def run(n, first, sync_grads=True):
         ctx = contextlib.nullcontext() if (sync_grads or world == 1) else model.no_sync()
@@ -254,7 +337,11 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
                     images, annos = pool[step % len(pool)]
                 if encoders is not None:
                     annos = encode_targets(encoders, *annos)
-                train_step(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None)
+                if device_step:
+                    train_step_device(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None,
+                                      args.max_grad_norm, world)
+                else:
+                    train_step(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None)
 
     def timed(n, first, **kw):
         sharding.barrier(dev if use_cuda else None)
@@ -268,6 +355,9 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
     del augment_events[:]
     step_s = timed(args.bench_steps, args.bench_warmup)
     extra = {}
+    if device_step:
+        extra['optimizer'] = 'device'
+        extra['dropped_steps'] = int(optimizer.dropped_steps)
     if augment is not None:
         torch.cuda.synchronize(dev)               # the events are complete before they are read
         us =[a.elapsed_time(b) * 1e3 for a, b in augment_events]
@@ -325,26 +415,14 @@ def main(argv=None):
         model = model.to(memory_format=torch.channels_last)
     if world > 1 and args.sync_bn:
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
-    params = [p for p in model.parameters() if p.requires_grad]
-    if args.optimizer == 'adam':
-        optimizer = torch.optim.Adam(params, lr=args.learning_rate * world, weight_decay=args.weight_decay, fused=use_cuda)
-    else:
-        optimizer = torch.optim.SGD(params, lr=args.learning_rate * world, momentum=args.momentum,
-                                    weight_decay=args.weight_decay)
+    if args.freeze:
+        freeze_backbone(model)
+    optimizer = make_optimizer(args, model, world, use_cuda)
     # continue a run (train_dist.py:219-233): weights, optimizer state and the epoch the LR schedule is at.  Before the DDP
     # wrap, so every rank loads the same state and the first broadcast has nothing to fix.
-    start_epoch = 0
-    if args.resume:
-        if not args.checkpoint_whole:
-            raise ValueError('--resume needs --checkpoint-whole <file>')
-        model, optimizer, start_epoch, start_loss, _ = models.load_model(
-            model, args.checkpoint_whole, optimizer=optimizer, resume_optimizer=True, drop_layers=False, optimizer2cuda=use_cuda)
-        if rank == 0:
-            print(f'resumed {args.checkpoint_whole}: next epoch {start_epoch}, last train loss {start_loss:.4f}')
-    elif args.checkpoint_whole:
-        # initialise from a checkpoint without its optimizer / epoch (fine-tuning, as evaluate.py:189-191 loads it); a path
-        # that does not exist is an error (load_model raises FileNotFoundError), never a silent random init
-        model, *_ = models.load_model(model, args.checkpoint_whole, optimizer=None, resume_optimizer=False, drop_layers=False)
+    model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda)
+    if args.resume and rank == 0:
+        print(f'resumed {args.checkpoint_whole}: next epoch {start_epoch}, last train loss {start_loss:.4f}')
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank] if use_cuda else None,
                                                           bucket_cap_mb=25, gradient_as_bucket_view=True)
@@ -401,8 +479,12 @@ def main(argv=None):
                 images, annos = pool[step % len(pool)]
             if encoders is not None:
                 annos = encode_targets(encoders, *annos)
-            loss, _ = train_step(model, criterion, optimizer, images, annos, args.lambdas,
-                                 torch.bfloat16 if use_cuda else None)
+            if args.device_step:
+                loss, _ = train_step_device(model, criterion, optimizer, images, annos, args.lambdas,
+                                            torch.bfloat16 if use_cuda else None, args.max_grad_norm, world)
+            else:
+                loss, _ = train_step(model, criterion, optimizer, images, annos, args.lambdas,
+                                     torch.bfloat16 if use_cuda else None)
             if step % args.print_freq == 0:
                 if world > 1:  # averaged over ranks for logging only (train_dist.py:346-348, :458-466)
                     torch.distributed.all_reduce(loss)
@@ -417,7 +499,9 @@ def main(argv=None):
                 losses.update(float(loss))
                 if rank == 0:
                     print(f'epoch {epoch} [{step}/{args.steps_per_epoch}] loss {losses.val:.4f} ({losses.avg:.4f}) '
-                          f'speed {world * args.batch_size / per_step:.1f} img/s')
+                          f'speed {world * args.batch_size / per_step:.1f} img/s'
+                          + (f' grad norm {float(optimizer.last_grad_norm):.4g} dropped {int(optimizer.dropped_steps)}'
+                             if args.device_step else ''))
         if rank == 0:
             models.save_model(os.path.join(args.checkpoint_path, f'PoseNet_{epoch}_epoch.pth'), epoch, losses.avg, model,
                               optimizer)
