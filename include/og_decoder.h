@@ -765,6 +765,28 @@ int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspa
  *     otherwise:        scale = 1
  * `loss`: device pointer to the weighted fp32 loss, or NULL.  DELIBERATE DIFFERENCE from torch: a non-finite norm (an inf or NaN
  * gradient anywhere) counts as a dropped batch; clip_grad_norm_ would multiply every gradient by NaN and poison every parameter.
+ * og_step_scale_amp_f32: og_step_scale_f32 behind a loss scaler (apex amp O1's LossScaler; optim.DeviceLossScaler): the gradients in the
+ * table are those of S * loss.  The same reduction in the same order gives n2, the sum of squares of the SCALED gradients.  `scaler`:
+ * a 16-byte, 16-byte aligned device block [S f32 (loss_scale), unskipped i32, overflows i32, last_overflow i32], owned by the caller.
+ * `loss` is the UNSCALED loss.  It writes the same state words the updates read, so they unscale and clip with one number and skip an
+ * overflow step through scale == 0.  Every line ONE rounded operation (fp32 unless it says double):
+ *     overflow = !isfinite(n2)
+ *     r = sqrt(n2) (double);  q = r / (double)S (double);  norm = (float)q               -- the reported norm is the unscaled one
+ *     overflow:             scale = 0;  last_overflow = 1
+ *       dynamic:            t = S / scale_factor;  S' = t < min_scale ? min_scale : t;  unskipped' = 0;  overflows += 1
+ *                           (`dropped` is NOT counted: a skipped overflow step is the scaler working, not an exploding batch)
+ *       static:             dropped += 1                                                 -- og_step_scale_f32's non-finite norm
+ *     no overflow:          last_overflow = 0
+ *       drop = loss != NULL && *loss > loss_limit
+ *       drop:               scale = 0;  dropped += 1
+ *       else:               inv = 1.f / S;  c = 1, or with a finite max_norm og_step_scale_f32's c from `norm`;  scale = c * inv
+ *       dynamic (dropped or not):  u = unskipped + 1;  if u == scale_window:  t = S * scale_factor;
+ *                           S' = t > max_scale ? max_scale : t;  u = 0;  then unskipped' = u
+ *   A static scaler (dynamic == 0) leaves S and unskipped alone.  With S a power of two every one of these operations is exact, so a
+ *   step on S * g equals the step on g bit for bit; S == 1 static is og_step_scale_f32.  apex 0.1's LossScaler defaults: S = 2^16,
+ *   scale_factor 2, scale_window 2000, min_scale 1, max_scale 2^24; this text is the specification (bit parity with apex: not pinned).
+ *   OG_EINVAL besides og_step_scale_f32's: a null or misaligned scaler block, scale_factor <= 1, scale_window < 1, min_scale <= 0,
+ *   max_scale < min_scale, a NaN or infinite one of them.  The block's contents are device memory and are not validated.
  * Updates: ONE launch over chunks chunk_first .. chunk_first + n_chunks of the table (a parameter group, or the parameters of one
  * step count, is a run of rows); scalars by value, computed by the host in double and rounded to fp32 once; `state` = the workspace
  * (scale is read from it) or NULL (scale = 1).  Every line is ONE individually rounded fp32 operation (-ffp-contract=off, correctly
@@ -796,6 +818,9 @@ int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_ro
                       size_t workspace_bytes, void *stream);
 int og_step_scale_f32(int n_chunks, const float *loss, float loss_limit, float max_norm, void *workspace, size_t workspace_bytes,
                       void *stream);
+int og_step_scale_amp_f32(int n_chunks, const float *loss, float loss_limit, float max_norm, void *scaler, int dynamic,
+                          float scale_factor, int scale_window, float min_scale, float max_scale, void *workspace,
+                          size_t workspace_bytes, void *stream);
 int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
                      float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1, float bc2, int adam_w_mode,
                      void *stream);

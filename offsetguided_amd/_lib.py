@@ -127,6 +127,7 @@ SIGNATURES = {
     "og_optim_workspace_bytes": (_sz, [_i]),
     "og_grad_sumsq_f32": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "og_step_scale_f32": (_i, [_i, _vp, _f, _f, _vp, _sz, _vp]),
+    "og_step_scale_amp_f32": (_i, [_i, _vp, _f, _f, _vp, _i, _f, _i, _f, _f, _vp, _sz, _vp]),
     "og_adam_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp]),
     "og_sgd_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp]),
 }

@@ -136,10 +136,9 @@ __global__ __launch_bounds__(OPTIM_THREADS) void grad_sumsq_kernel(const int64_t
 
 // ---- the scale block -----------------------------------------------------------------------------------------------------------
 // One workgroup.  Thread t sums its contiguous share of the partials in index order; the 1024 thread sums are added in index order
-// sixteen at a time by wave 0, whose lanes are folded by a shuffle tree: one fixed order for a given number of partials.
-__global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double *__restrict__ partials, int n_partials,
-                                                                   const float *__restrict__ loss, float loss_limit, float max_norm,
-                                                                   float *__restrict__ state)
+// sixteen at a time by wave 0, whose lanes are folded by a shuffle tree: one fixed order for a given number of partials.  True on
+// thread 0 alone, which then holds the sum in n2.
+__device__ __forceinline__ bool sum_partials(const double *__restrict__ partials, int n_partials, double &n2)
 {
     __shared__ double sums[SCALE_THREADS];
     const int per = (n_partials + SCALE_THREADS - 1) / SCALE_THREADS;
@@ -149,26 +148,94 @@ __global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double 
     for (int i = first; i < last; ++i) acc += partials[i];
     sums[threadIdx.x] = acc;
     __syncthreads();
-    if (threadIdx.x < 64) {
-        double a = 0.0;
-        for (int i = 0; i < SCALE_THREADS / 64; ++i) a += sums[threadIdx.x * (SCALE_THREADS / 64) + i];
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-        if (threadIdx.x == 0) {
-            const double n2 = a;
-            const float norm = (float)sqrt(n2);
-            const bool drop = (loss != nullptr && *loss > loss_limit) || !isfinite(n2);
-            float scale = 1.f;
-            if (drop) {
-                scale = 0.f;
-            } else if (isfinite(max_norm)) {
-                const float den = norm + 1e-6f;
-                const float c = max_norm / den;
-                scale = c < 1.f ? c : 1.f;
-            }
-            state[0] = scale;
-            state[1] = norm;
-            if (drop) reinterpret_cast<int *>(state)[2] += 1;
+    if (threadIdx.x >= 64) return false;
+    double a = 0.0;
+    for (int i = 0; i < SCALE_THREADS / 64; ++i) a += sums[threadIdx.x * (SCALE_THREADS / 64) + i];
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    n2 = a;
+    return threadIdx.x == 0;
+}
+
+// c of torch.nn.utils.clip_grad_norm_ from the fp32 norm
+__device__ __forceinline__ float clip_coefficient(float norm, float max_norm)
+{
+    if (!isfinite(max_norm)) return 1.f;
+    const float den = norm + 1e-6f;
+    const float c = max_norm / den;
+    return c < 1.f ? c : 1.f;
+}
+
+__global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double *__restrict__ partials, int n_partials,
+                                                                   const float *__restrict__ loss, float loss_limit, float max_norm,
+                                                                   float *__restrict__ state)
+{
+    double n2;
+    if (!sum_partials(partials, n_partials, n2)) return;
+    const float norm = (float)sqrt(n2);
+    const bool drop = (loss != nullptr && *loss > loss_limit) || !isfinite(n2);
+    const float scale = drop ? 0.f : clip_coefficient(norm, max_norm);
+    state[0] = scale;
+    state[1] = norm;
+    if (drop) reinterpret_cast<int *>(state)[2] += 1;
+}
+
+// The same block behind a loss scaler (header: og_step_scale_amp_f32): the gradients carry the factor S = scaler[0]; the scale it
+// writes unscales and clips in one number, an overflow skips the step and moves S.  Plain loads and stores by thread 0.
+struct AmpArgs {
+    int dynamic;
+    float factor;
+    int window;
+    float min_scale, max_scale;
+};
+
+__global__ __launch_bounds__(SCALE_THREADS) void step_scale_amp_kernel(const double *__restrict__ partials, int n_partials,
+                                                                       const float *__restrict__ loss, float loss_limit, float max_norm,
+                                                                       float *__restrict__ state, float *__restrict__ scaler, AmpArgs a)
+{
+    double n2;
+    if (!sum_partials(partials, n_partials, n2)) return;
+    int *dropped = reinterpret_cast<int *>(state) + 2;
+    int *words = reinterpret_cast<int *>(scaler);          // [1] unskipped, [2] overflows, [3] last_overflow
+    const float S = scaler[0];
+    const bool overflow = !isfinite(n2);
+    const double root = sqrt(n2);
+    const double unscaled = root / (double)S;
+    const float norm = (float)unscaled;
+    float scale = 0.f, next = S;
+    int u = words[1];
+    if (overflow) {
+        words[3] = 1;
+        if (a.dynamic) {
+            const float t = S / a.factor;
+            next = t < a.min_scale ? a.min_scale : t;
+            u = 0;
+            words[2] += 1;
+        } else {
+            *dropped += 1;
         }
+    } else {
+        words[3] = 0;
+        if (loss != nullptr && *loss > loss_limit) {
+            *dropped += 1;
+        } else {
+            const float inv = 1.f / S;
+            const float c = clip_coefficient(norm, max_norm);
+            scale = c * inv;
+        }
+        if (a.dynamic) {
+            u = u + 1;
+            if (u == a.window) {
+                const float t = S * a.factor;
+                next = t > a.max_scale ? a.max_scale : t;
+                u = 0;
+            }
+        }
+    }
+    state[0] = scale;
+    state[1] = norm;
+    if (a.dynamic) {
+        scaler[0] = next;
+        words[1] = u;
     }
 }
 
@@ -355,6 +422,34 @@ OG_API int og_step_scale_f32(int n_chunks, const float *loss, float loss_limit, 
     const double *partials = reinterpret_cast<const double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
     hipLaunchKernelGGL(step_scale_kernel, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss, loss_limit,
                        max_norm, state);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
+OG_API int og_step_scale_amp_f32(int n_chunks, const float *loss, float loss_limit, float max_norm, void *scaler, int dynamic,
+                                 float scale_factor, int scale_window, float min_scale, float max_scale, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    const char *name = "og_step_scale_amp_f32";
+    OG_REQUIRE(n_chunks >= 0, OG_EINVAL, "%s: negative chunk count", name);
+    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
+    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
+               workspace_bytes, og_optim_workspace_bytes(n_chunks));
+    OG_REQUIRE(!(max_norm != max_norm) && !(loss_limit != loss_limit), OG_EINVAL, "%s: NaN max_norm or loss_limit", name);
+    OG_REQUIRE(((uintptr_t)loss & 3u) == 0, OG_EINVAL, "%s: misaligned loss", name);
+    OG_REQUIRE(scaler && ((uintptr_t)scaler & 15u) == 0, OG_EINVAL, "%s: null or misaligned scaler block", name);
+    // written so that a NaN fails each of them
+    OG_REQUIRE(scale_factor > 1.f && scale_factor <= 3.4028234664e38f, OG_EINVAL, "%s: scale_factor must be a finite number above 1 (got %g)",
+               name, scale_factor);
+    OG_REQUIRE(scale_window >= 1, OG_EINVAL, "%s: scale_window must be at least 1 (got %d)", name, scale_window);
+    OG_REQUIRE(min_scale > 0.f, OG_EINVAL, "%s: min_scale must be positive (got %g)", name, min_scale);
+    OG_REQUIRE(max_scale >= min_scale && max_scale <= 3.4028234664e38f, OG_EINVAL, "%s: max_scale must be finite and not below min_scale (got %g, %g)",
+               name, max_scale, min_scale);
+    float *state = static_cast<float *>(workspace);
+    const double *partials = reinterpret_cast<const double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
+    const AmpArgs a{dynamic != 0, scale_factor, scale_window, min_scale, max_scale};
+    hipLaunchKernelGGL(step_scale_amp_kernel, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss, loss_limit,
+                       max_norm, state, static_cast<float *>(scaler), a);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }

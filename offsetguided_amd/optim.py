@@ -4,7 +4,8 @@ DeviceSGD on the multi-tensor HIP kernels of csrc/optim.hip (include/og_decoder.
 step(loss=..., max_grad_norm=...) queues three launches on the current stream: the sum of squares of every gradient, the scale block
 (the clip coefficient of torch.nn.utils.clip_grad_norm_ and the reference's `loss > 1e8` batch drop in ONE device-side number), and
 the update, which multiplies every gradient by that number.  Nothing is read back: `last_grad_norm` and `dropped_steps` are device
-tensors the caller converts when it prints.
+tensors the caller converts when it prints.  step(..., scaler=DeviceLossScaler()) is the fp16 form (apex amp O1's dynamic loss
+scaling, train_dist.py:336): the scale block also unscales, skips a step whose gradients overflowed and moves the loss scale.
 
 The state keys are torch's (`step`, `exp_avg`, `exp_avg_sq`, `momentum_buffer`): a checkpoint written with torch.optim.Adam / SGD
 resumes here and the other way round.  `step` is counted on the host; the tensors under state[p]['step'] are brought up to date by
@@ -44,6 +45,92 @@ class _TableSlot:
 
     def free(self):
         return self.event is None or self.event.query()
+
+
+class DeviceLossScaler:
+    """apex amp O1's LossScaler with its state on the device: a 16-byte block [loss_scale f32, unskipped i32, overflows i32,
+    last_overflow i32] that og_step_scale_amp_f32 reads and moves inside the optimizer's step (include/og_decoder.h has the rule).
+    loss_scale: 'dynamic' (start at init_scale, divide by scale_factor on an overflow, multiply after scale_window clean steps,
+    inside [min_loss_scale, max_loss_scale]) or a number (static).  Only state_dict() reads anything back."""
+
+    def __init__(self, loss_scale='dynamic', init_scale=2. ** 16, scale_factor=2., scale_window=2000, min_loss_scale=1.,
+                 max_loss_scale=2. ** 24, device=None):
+        self.dynamic = loss_scale == 'dynamic'
+        start = float(init_scale if self.dynamic else loss_scale)
+        min_loss_scale = 1. if min_loss_scale is None else min_loss_scale      # apex: None = no lower bound; a scale stays positive here
+        numbers = (start, scale_factor, min_loss_scale, max_loss_scale)
+        if not all(math.isfinite(x) for x in numbers) or not (start > 0 and scale_factor > 1 and int(scale_window) >= 1
+                                                              and min_loss_scale > 0 and max_loss_scale >= min_loss_scale):
+            raise ValueError(f'DeviceLossScaler: bad hyper-parameters loss_scale={loss_scale} init_scale={init_scale} '
+                             f'scale_factor={scale_factor} scale_window={scale_window} min_loss_scale={min_loss_scale} '
+                             f'max_loss_scale={max_loss_scale}')
+        self.scale_factor, self.scale_window = float(scale_factor), int(scale_window)
+        self.min_loss_scale, self.max_loss_scale = float(min_loss_scale), float(max_loss_scale)
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        # a tensor of its own, never a slice of the optimizer's workspace (that one is reallocated when the parameter list grows)
+        self._block = self._words(start, 0, 0, 0).to(self.device)
+
+    @staticmethod
+    def _words(loss_scale, unskipped, overflows, last_overflow):
+        words = np.array([0, unskipped, overflows, last_overflow], dtype=np.int32)
+        words[:1].view(np.float32)[0] = loss_scale
+        return torch.from_numpy(words)
+
+    def scale(self, loss):
+        """loss * loss_scale, a product of device tensors: call backward() on it."""
+        return loss * self.loss_scale
+
+    @property
+    def loss_scale(self):
+        """fp32 device scalar: the factor the next backward's gradients carry."""
+        return self._block[0:1].view(torch.float32)[0]
+
+    @property
+    def unskipped(self):
+        """int32 device scalar: steps without an overflow since the scale last moved (dynamic)."""
+        return self._block[1]
+
+    @property
+    def overflow_steps(self):
+        """int32 device scalar: steps a dynamic scaler skipped for a non-finite gradient."""
+        return self._block[2]
+
+    @property
+    def last_overflow(self):
+        """int32 device scalar: 1 when the last step met a non-finite gradient."""
+        return self._block[3]
+
+    def state_dict(self):
+        """apex's keys.  The one read-back: called when a checkpoint is written."""
+        host = self._block.cpu()
+        return {'loss_scale': float(host[0:1].view(torch.float32)[0]), 'unskipped': int(host[1])}
+
+    def load_state_dict(self, state):
+        """Scale and window position of a checkpoint (as apex does, also into a static scaler: the run goes on at the scale it had)."""
+        scale, unskipped = float(state['loss_scale']), int(state['unskipped'])
+        if not (math.isfinite(scale) and scale > 0 and unskipped >= 0):
+            raise ValueError(f'DeviceLossScaler: bad state loss_scale={scale} unskipped={unskipped}')
+        self._block[:2].copy_(self._words(scale, unskipped, 0, 0)[:2])
+
+
+def amp_state_dict(scaler):
+    """The layout of apex's amp.state_dict() with one loss scaler: save_model(amp_state=...) writes it as the checkpoint's `amp`."""
+    return {'loss_scaler0': scaler.state_dict()}
+
+
+def load_amp_state(scaler, state):
+    """The `amp` entry of a checkpoint (load_model(load_amp=True)'s last result; False when the file has none) into the scaler.
+    -> whether a state was loaded."""
+    if not state:
+        return False
+    if 'loss_scaler0' not in state:
+        raise ValueError(f"amp state without 'loss_scaler0' (keys {sorted(state)})")
+    scaler.load_state_dict(state['loss_scaler0'])
+    return True
 
 
 class _DeviceOptimizer(torch.optim.Optimizer):
@@ -195,9 +282,11 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         self._signature = signature
 
     @torch.no_grad()
-    def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8):
+    def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8, scaler=None):
         """Queue one optimisation step on the current stream.  loss: the weighted fp32 loss on the device (a batch whose loss exceeds
         loss_limit is dropped); max_grad_norm: clip_grad_norm_'s max_norm over every gradient.  With neither, only the update runs.
+        scaler: the DeviceLossScaler whose scale(loss) was sent backward -- the sum of squares always runs, the scale block unscales
+        (and clips) with one number, skips the step on a non-finite gradient and moves the loss scale; loss is the unscaled one.
         Never waits for the device."""
         out = None
         if closure is not None:
@@ -206,6 +295,9 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         if max_grad_norm != max_grad_norm or max_grad_norm <= 0:
             raise ValueError(f'max_grad_norm must be positive, got {max_grad_norm}')
         dev = self._device()
+        if scaler is not None and scaler.device != dev:
+            raise _lib.OgError(f'{type(self).__name__}.step: loss scaler on {scaler.device}, parameters on {dev}; the scale block reads '
+                               'the scaler on the device it runs on')
         lib = _lib.load()
         entries = self._entries(dev)
         if not entries:
@@ -216,14 +308,21 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             stream = _lib.stream_ptr(dev)
             rows, prefix = self._table.data_ptr(), self._table.data_ptr() + 40 * self._n_rows
             state_ptr = None
-            if loss is not None or math.isfinite(max_grad_norm):
+            if loss is not None or math.isfinite(max_grad_norm) or scaler is not None:
                 if loss is not None:
                     loss = _lib.require_device(loss.detach(), 'loss')
                     if loss.numel() != 1:
                         raise ValueError(f'loss: one element expected, got {tuple(loss.shape)}')
                 _lib.check(lib.og_grad_sumsq_f32(rows, prefix, self._n_rows, self._n_chunks, _lib.ptr(ws), ws.numel(), stream), lib)
-                _lib.check(lib.og_step_scale_f32(self._n_chunks, _lib.ptr(loss) if loss is not None else None, loss_limit, max_grad_norm,
-                                                 _lib.ptr(ws), ws.numel(), stream), lib)
+                loss_ptr = _lib.ptr(loss) if loss is not None else None
+                if scaler is None:
+                    _lib.check(lib.og_step_scale_f32(self._n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(ws), ws.numel(),
+                                                     stream), lib)
+                else:
+                    _lib.check(lib.og_step_scale_amp_f32(self._n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(scaler._block),
+                                                         int(scaler.dynamic), scaler.scale_factor, scaler.scale_window,
+                                                         scaler.min_loss_scale, scaler.max_loss_scale, _lib.ptr(ws), ws.numel(),
+                                                         stream), lib)
                 state_ptr = _lib.ptr(ws)
             for gi, key, first, count in self._segments:
                 self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream)

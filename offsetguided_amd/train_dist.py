@@ -1,6 +1,7 @@
 """Data-parallel training step (reference train_dist.py:108-387), MI355X-native:
 
-  apex AMP O1 + dynamic loss scaling      -> torch.autocast(bfloat16) (no scaler needed)
+  apex AMP O1 + dynamic loss scaling      -> torch.autocast(bfloat16) (no scaler needed); --opt-level O1: torch.autocast(float16) and
+    (amp.scale_loss, :336)                    optim.DeviceLossScaler, whose unscale / overflow skip / scale update run inside the step
   apex DistributedDataParallel            -> torch DDP over RCCL/xGMI: 25 MB gradient buckets whose
     (delay_allreduce=True: one flat            all-reduce overlaps the rest of backward (xGMI links are
      all-reduce after backward)                point-to-point, so overlap matters more than on NVSwitch)
@@ -87,7 +88,31 @@ def train_cli(argv=None):
                         'gradient clipping are one device-side scale, losses stay on the device between --print-freq lines')
     g.add_argument('--max-grad-norm', default=float('inf'), type=float,
                    help='clip the norm of all gradients to this value, as torch.nn.utils.clip_grad_norm_ does (with --device-step)')
+    g = p.add_argument_group('apex configuration (train_dist.py:77-82)')
+    g.add_argument('--opt-level', type=str, default=None, choices=['O0', 'O1', 'O2', 'O3'],
+                   help='O0: fp32, no autocast; O1: fp16 autocast with a device-side loss scaler (optim.DeviceLossScaler, needs '
+                        '--device-step); not given: bf16 autocast, no scaler.  O2 / O3 are not implemented.  With --grad-compress bf16 '
+                        'the DDP hook rounds the SCALED gradients to bf16: bf16 has fp32\'s exponent range, so the scale costs no range '
+                        'and the rounding is the same relative one as without a scaler -- the two flags combine')
+    g.add_argument('--loss-scale', type=str, default=None, metavar="{dynamic,NUMBER}",
+                   help='with --opt-level O1: dynamic loss scaling (not given, or "dynamic") or a static scale')
+    g.add_argument('--drop-amp-state', dest='load_amp', action='store_false', default=True,
+                   help="do not resume the loss scaler from the checkpoint's amp entry")
     args = p.parse_args(argv)
+    if args.opt_level in ('O2', 'O3'):
+        p.error(f'--opt-level {args.opt_level} is not implemented: it needs fp16 model copies with fp32 master weights (O0 and O1 are)')
+    if args.opt_level == 'O1' and not args.device_step:
+        p.error('--opt-level O1 unscales and skips overflow steps inside the device-side step: add --device-step')
+    if args.loss_scale is not None:
+        if args.opt_level != 'O1':
+            p.error('--loss-scale belongs to --opt-level O1')
+        if args.loss_scale != 'dynamic':
+            try:
+                args.loss_scale = float(args.loss_scale)
+            except ValueError:
+                p.error(f"--loss-scale: 'dynamic' or a number, got {args.loss_scale!r}")
+            if not 0 < args.loss_scale < float('inf'):
+                p.error('--loss-scale must be positive and finite')
     if args.max_grad_norm != float('inf') and not args.device_step:
         p.error('--max-grad-norm is applied by the device-side step: add --device-step')
     if not args.max_grad_norm > 0:
@@ -213,6 +238,17 @@ def encode_targets(encoders, joints, n_persons, mask_miss=None):
     return [(hm, bg if bg.numel() else None, jit if jit.numel() else None, mask), (off, sc if sc.numel() else None, ps, mask)]
 
 
+def amp_setup(args, dev, use_cuda):
+    """--opt-level -> (autocast dtype or None, loss scaler or None).  Not given: the bf16 autocast of every run so far, no scaler."""
+    level = getattr(args, 'opt_level', None)
+    if level is None:
+        return (torch.bfloat16 if use_cuda else None), None
+    if level == 'O0':
+        return None, None
+    loss_scale = getattr(args, 'loss_scale', None)
+    return torch.float16, optim.DeviceLossScaler('dynamic' if loss_scale is None else loss_scale, device=dev)
+
+
 def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dtype=torch.bfloat16):
     """One optimisation step (train_dist.py:304-342).  Returns (loss, per-head losses)."""
     optimizer.zero_grad(set_to_none=True)
@@ -233,12 +269,15 @@ def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dty
 
 
 def train_step_device(model, criterion, optimizer, images, annos, lambdas, autocast_dtype=torch.bfloat16, max_grad_norm=float('inf'),
-                      world=1):
+                      world=1, scaler=None):
     """train_step for optim.DeviceAdam / DeviceSGD: nothing is read back.  backward() runs on the real loss; the step multiplies the
     gradients by the device-side scale -- 0 for a batch whose loss exceeds 1e8 (train_dist.py:322-325) or whose gradients are not
     finite, the clip_grad_norm_ coefficient of --max-grad-norm otherwise.  Under DDP the gradients are all-reduced when backward()
     returns, so every rank takes the same norm; the loss the drop looks at is the largest over the ranks, so every rank drops the same
-    batches.  Returns (loss, per-head losses) as device tensors."""
+    batches.  scaler (optim.DeviceLossScaler, --opt-level O1): backward() runs on scaler.scale(loss); the step unscales, and a step
+    whose gradients overflowed is skipped and moves the loss scale; the drop still looks at the unscaled loss.  Under DDP an inf or
+    NaN in any rank's gradients is non-finite on every rank after the all-reduce, so every rank takes the same decision and keeps the
+    same loss scale without another collective.  Returns (loss, per-head losses) as device tensors."""
     optimizer.zero_grad(set_to_none=True)
     dev_type = 'cuda' if images.is_cuda else 'cpu'
     with torch.autocast(dev_type, dtype=autocast_dtype, enabled=autocast_dtype is not None):
@@ -249,13 +288,16 @@ def train_step_device(model, criterion, optimizer, images, annos, lambdas, autoc
         multi_losses += list(lossfun(out32, *anno))
     assert len(multi_losses) <= len(lambdas), 'lambdas is incomplete'
     loss = sum(lam * l for lam, l in zip(lambdas, multi_losses))
-    loss.backward()
+    (loss if scaler is None else scaler.scale(loss)).backward()
     loss = loss.detach()
     guard = loss
     if world > 1:
         guard = loss.clone()
         torch.distributed.all_reduce(guard, op=torch.distributed.ReduceOp.MAX)
-    optimizer.step(loss=guard, max_grad_norm=max_grad_norm)
+    if scaler is None:
+        optimizer.step(loss=guard, max_grad_norm=max_grad_norm)
+    else:
+        optimizer.step(loss=guard, max_grad_norm=max_grad_norm, scaler=scaler)
     return loss, [l.detach() if torch.is_tensor(l) else l for l in multi_losses]
 
 
@@ -280,18 +322,21 @@ def make_optimizer(args, model, world, use_cuda):
     return torch.optim.SGD(params, lr=lr, momentum=args.momentum, weight_decay=args.weight_decay)
 
 
-def load_checkpoint(args, model, optimizer, use_cuda):
+def load_checkpoint(args, model, optimizer, use_cuda, scaler=None):
     """--resume (train_dist.py:230-236, :267-268): weights, optimizer state unless --drop-optim-state, and the epoch the LR schedule
     is at unless --recount-epoch.  Without --resume, --checkpoint-whole initialises the weights only (fine-tuning, as
     evaluate.py:189-191 loads it); a path that does not exist is an error (load_model raises FileNotFoundError), never a silent
-    random init.  -> (model, optimizer, start_epoch, start_loss or None)."""
+    random init.  scaler: resumed from the checkpoint's `amp` entry (train_dist.py:234-236) unless --drop-amp-state; a checkpoint
+    without one leaves it as made.  -> (model, optimizer, start_epoch, start_loss or None)."""
     drop_layers = getattr(args, 'drop_layers', False)
     if args.resume:
         if not args.checkpoint_whole:
             raise ValueError('--resume needs --checkpoint-whole <file>')
-        model, optimizer, start_epoch, start_loss, _ = models.load_model(
+        model, optimizer, start_epoch, start_loss, amp_state = models.load_model(
             model, args.checkpoint_whole, optimizer=optimizer, resume_optimizer=getattr(args, 'resume_optimizer', True),
-            drop_layers=drop_layers, optimizer2cuda=use_cuda)
+            drop_layers=drop_layers, optimizer2cuda=use_cuda, load_amp=scaler is not None and getattr(args, 'load_amp', True))
+        if scaler is not None:
+            optim.load_amp_state(scaler, amp_state)
         return model, optimizer, 0 if getattr(args, 'recount_epoch', False) else start_epoch, start_loss
     if args.checkpoint_whole:
         model, *_ = models.load_model(model, args.checkpoint_whole, optimizer=None, resume_optimizer=False, drop_layers=drop_layers)
@@ -313,12 +358,12 @@ def describe_losses(args):
     return ' + '.join(parts) + ' losses' + (', sqrt' if args.sqrt_re else '') + ('' if args.fused_losses else ', torch-formulated')
 
 
-def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment=None, rng=None):
+def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment=None, rng=None, amp=None):
     """BASELINE configs[4]: step time of the DDP training step (fused HIP losses, device-side GT encoding, bf16 autocast)
     and the gradient all-reduce's bus bandwidth.  The all-reduce overlaps backward inside the step, so its bandwidth is
     measured on its own: the same payload (one flat buffer of the gradients' size, the bucketed hook's dtype) reduced
     back to back over RCCL; bus GB/s = bytes x 2 (N - 1) / N / time (ring convention).  `exposed_comm_ms` = step time
-    minus the same step under no_sync()."""
+    minus the same step under no_sync().  amp: amp_setup's pair; None = bf16 autocast, no scaler."""
     import contextlib
     import json
     use_cuda = dev.type == 'cuda'
@@ -326,6 +371,7 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
 
     augment_events = []
     device_step = getattr(args, 'device_step', False)
+    autocast_dtype, scaler = amp if amp is not None else (torch.bfloat16 if use_cuda else None, None)
 
     def run(n, first, sync_grads=True):
         ctx = contextlib.nullcontext() if (sync_grads or world == 1) else model.no_sync()
@@ -338,10 +384,10 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
                 if encoders is not None:
                     annos = encode_targets(encoders, *annos)
                 if device_step:
-                    train_step_device(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None,
-                                      args.max_grad_norm, world)
+                    train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype, args.max_grad_norm,
+                                      world, scaler)
                 else:
-                    train_step(model, criterion, optimizer, images, annos, args.lambdas, torch.bfloat16 if use_cuda else None)
+                    train_step(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype)
 
     def timed(n, first, **kw):
         sharding.barrier(dev if use_cuda else None)
@@ -358,6 +404,10 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
     if device_step:
         extra['optimizer'] = 'device'
         extra['dropped_steps'] = int(optimizer.dropped_steps)
+    if scaler is not None:
+        extra['amp'] = 'fp16'
+        extra['loss_scale'] = float(scaler.loss_scale)
+        extra['overflow_steps'] = int(scaler.overflow_steps)
     if augment is not None:
         torch.cuda.synchronize(dev)               # the events are complete before they are read
         us =[a.elapsed_time(b) * 1e3 for a, b in augment_events]
@@ -382,6 +432,8 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
         comm_s = sharding.max_over_ranks(time.perf_counter() - t0, dev if use_cuda else None) / reps
         comm_ms, bus = round(comm_s * 1e3, 3), round(nbytes * 2 * (world - 1) / world / comm_s / 1e9, 1)
     group = sharding.describe_group(dev if use_cuda else None)   # every rank takes part in the gather
+    autocast_name = 'bf16 autocast' if amp is None else {torch.bfloat16: 'bf16 autocast', torch.float16: 'fp16 autocast + loss scaler',
+                                                        None: 'fp32, no autocast'}[autocast_dtype]
     if rank == 0:
         print(json.dumps({
             'rccl': group,
@@ -389,7 +441,7 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
             'value': round(world * args.batch_size / step_s, 2), 'unit': 'images/sec', 'n_gpus': world,
             'steps': args.bench_steps, 'warmup': args.bench_warmup, 'ms_per_step': round(step_s * 1e3, 2),
             'config': {'workload': f'train_dist DDP, {args.square_length}x{args.square_length} crops, bs{args.batch_size}/GPU, '
-                                   f'bf16 autocast, {describe_losses(args)} (BASELINE configs[4])',
+                                   f'{autocast_name}, {describe_losses(args)} (BASELINE configs[4])',
                        'sync_bn': bool(args.sync_bn and world > 1), 'grad_payload': str(payload_dtype).replace('torch.', '')},
             'grad_allreduce': {'bytes': nbytes, 'ms': comm_ms, 'bus_GBps': bus,
                                'exposed_comm_ms': round(max(step_s - nosync_s, 0.0) * 1e3, 2) if world > 1 else 0.0},
@@ -418,9 +470,10 @@ def main(argv=None):
     if args.freeze:
         freeze_backbone(model)
     optimizer = make_optimizer(args, model, world, use_cuda)
+    autocast_dtype, scaler = amp_setup(args, dev, use_cuda)
     # continue a run (train_dist.py:219-233): weights, optimizer state and the epoch the LR schedule is at.  Before the DDP
     # wrap, so every rank loads the same state and the first broadcast has nothing to fix.
-    model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda)
+    model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda, scaler)
     if args.resume and rank == 0:
         print(f'resumed {args.checkpoint_whole}: next epoch {start_epoch}, last train loss {start_loss:.4f}')
     if world > 1:
@@ -465,7 +518,8 @@ def main(argv=None):
                                                  background=args.include_background, jitter=args.include_jitter_offset,
                                                  scale=args.include_scale)))
     if args.bench:
-        return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment, aug_rng)
+        return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment, aug_rng,
+                           None if args.opt_level is None else (autocast_dtype, scaler))
     batch_time = AverageMeter()   # over the whole run: the first steps (MIOpen find, allocator warm-up) do not bias an epoch
     # --epochs MORE epochs after a resume, as the reference counts them (train_dist.py:269)
     for epoch in range(start_epoch, start_epoch + args.epochs):
@@ -480,11 +534,10 @@ def main(argv=None):
             if encoders is not None:
                 annos = encode_targets(encoders, *annos)
             if args.device_step:
-                loss, _ = train_step_device(model, criterion, optimizer, images, annos, args.lambdas,
-                                            torch.bfloat16 if use_cuda else None, args.max_grad_norm, world)
+                loss, _ = train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype,
+                                            args.max_grad_norm, world, scaler)
             else:
-                loss, _ = train_step(model, criterion, optimizer, images, annos, args.lambdas,
-                                     torch.bfloat16 if use_cuda else None)
+                loss, _ = train_step(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype)
             if step % args.print_freq == 0:
                 if world > 1:  # averaged over ranks for logging only (train_dist.py:346-348, :458-466)
                     torch.distributed.all_reduce(loss)
@@ -501,10 +554,12 @@ def main(argv=None):
                     print(f'epoch {epoch} [{step}/{args.steps_per_epoch}] loss {losses.val:.4f} ({losses.avg:.4f}) '
                           f'speed {world * args.batch_size / per_step:.1f} img/s'
                           + (f' grad norm {float(optimizer.last_grad_norm):.4g} dropped {int(optimizer.dropped_steps)}'
-                             if args.device_step else ''))
+                             if args.device_step else '')
+                          + (f' loss scale {float(scaler.loss_scale):g} overflows {int(scaler.overflow_steps)}'
+                             if scaler is not None else ''))
         if rank == 0:
             models.save_model(os.path.join(args.checkpoint_path, f'PoseNet_{epoch}_epoch.pth'), epoch, losses.avg, model,
-                              optimizer)
+                              optimizer, amp_state=optim.amp_state_dict(scaler) if scaler is not None else None)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
