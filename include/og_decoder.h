@@ -827,6 +827,36 @@ int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_row
 int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
                     float lr, float mom, float wd, int first, void *stream);
 
+/* ---- weight refresh: BatchNorm fold + 16-bit cast of every layer in one launch (models/engine.py: InferenceEngine.refresh;
+ * csrc/fold.hip) ----  What an engine computes with torch ops when it is built (_fold, .to(dtype), channels-last), written into the
+ * buffers it already has, so that captured graphs keep their addresses.  Table (device memory, filled by the caller in pinned memory
+ * and copied once): `rows` int64[n_rows][og_fold_row_words() = 16], one row per convolution:
+ *     [0] w       fp32 weight (Cout, Cin, kh, kw), dense; 4-byte aligned, any offset beyond that
+ *     [1] bias    fp32 (Cout) or 0
+ *     [2..5]      BatchNorm weight (gamma), bias (beta), running_mean, running_var, fp32 (Cout) each; all four or all 0 (no BN)
+ *     [6] dst w   16-bit (Cout, kh, kw, Cin): the memory of a channels-last (Cout, Cin, kh, kw) tensor
+ *     [7] dst b32 fp32 (Cout) or 0      [8] dst b  16-bit (Cout) or 0
+ *     [9] Cout    [10] Cin    [11] kh * kw    [12] bit 0: the source's memory is channels-last ((Cout, kh, kw, Cin)), else OIHW
+ *     [13] eps    the fp32 bit pattern of the BatchNorm's eps (the double rounded once)
+ *     [14] partner  row whose b' is added to this row's (same Cout), or -1: the layer whose output meets this one's before the
+ *                 activation (a residual's projection on conv2, the junction's cnvs_ on inters_)
+ *     [15] slab   output channels per workgroup (> 0); the row has ceil(Cout / slab) workgroups
+ * `wg_prefix` int32[n_rows + 1]: the running sum of the rows' workgroup counts from 0 to n_workgroups.  The rule, per output channel
+ * o, every line ONE rounded fp32 operation (-ffp-contract=off, correctly rounded divide and sqrt):
+ *     s = var[o] + eps;  r = sqrt(s);  scale = gamma[o] / r            (no BN: no scale, w' = w, b' = bias or 0)
+ *     w' = w * scale                    then round-to-nearest-even to the 16-bit type
+ *     d = bias[o] - mean[o] (bias = 0 without one);  m = d * scale;  b' = m + beta[o]
+ *     partner:  b' = b'(this row) + b'(partner row)
+ *     dst b32 = b';  dst b = b' rounded to the 16-bit type
+ * f16 != 0: fp16 (a value beyond its range becomes inf, as torch's cast; subnormals are kept), else bf16 (a NaN becomes 0x7fc0), for
+ * the whole launch.  A workgroup reads each output channel's weights as one contiguous run (16-byte loads where the address allows)
+ * and writes 16-byte stores where dst w is 16-byte aligned and Cin (channels-last source or 1x1: Cin * kh * kw) is a multiple of 8;
+ * an OIHW source is permuted through LDS.  A row with more than 512 taps, or whose workgroup falls outside it, is left alone.  No
+ * allocation, no synchronisation.  OG_EINVAL (nothing launched): a null or misaligned table, n_rows <= 0, a negative workgroup
+ * count.  The table's contents are device memory and are not validated: its builder answers for addresses, shapes and counts. */
+int og_fold_row_words(void);
+int og_fold_bn_w16(const int64_t *rows, const int32_t *wg_prefix, int n_rows, int n_workgroups, int f16, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

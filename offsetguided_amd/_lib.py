@@ -130,6 +130,8 @@ SIGNATURES = {
     "og_step_scale_amp_f32": (_i, [_i, _vp, _f, _f, _vp, _i, _f, _i, _f, _f, _vp, _sz, _vp]),
     "og_adam_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp]),
     "og_sgd_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp]),
+    "og_fold_row_words": (_i, []),
+    "og_fold_bn_w16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

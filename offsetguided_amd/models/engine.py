@@ -37,6 +37,7 @@ import weakref
 
 import torch
 import torch.nn.functional as F
+from torch.nn.modules.batchnorm import _BatchNorm
 
 from .. import _lib
 from .hourglass_104 import ConvBlock, HourglassLevel, Residual
@@ -47,12 +48,24 @@ def _fold(conv, bn):
     (weight, bias) fp32 on the engine's device.  Reads the module, never modifies or moves it."""
     w = conv.weight.detach().float()
     b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0], device=w.device)
-    if isinstance(bn, torch.nn.BatchNorm2d):
-        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    if isinstance(bn, _BatchNorm):        # BatchNorm2d and SyncBatchNorm alike (the latter is not a BatchNorm2d)
+        # scale = gamma / sqrt(var + eps) as correctly rounded fp32 operations, the rule og_fold_bn_w16 follows (include/og_decoder.h):
+        # torch's CPU fp32 sqrt is not (it misses the last bit of 0.6 % of a long tensor's elements; its divide, and the device's sqrt
+        # and divide on the 65 536 values tried, are), so the root and the quotient are taken in double and rounded once, which is
+        # the correctly rounded fp32 result -- an engine built from a module equals one refreshed from it, on whichever device
+        # the module lives
+        s = bn.running_var.detach().float() + bn.eps
+        scale = (bn.weight.detach().double() / torch.sqrt(s.double()).float().double()).float()
         w = w * scale[:, None, None, None]
         b = (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
     if _issuer.build_device is not None:   # the engine under construction on this thread
         w, b = w.to(_issuer.build_device), b.to(_issuer.build_device)
+    # a layer without BatchNorm whose parameters are fp32 on that device (the heads of an fp32 engine) comes through untouched: the
+    # bundle keeps, and refresh() overwrites, storage of its own, never the module's
+    if w.data_ptr() == conv.weight.data_ptr():
+        w = w.clone()
+    if conv.bias is not None and b.data_ptr() == conv.bias.data_ptr():
+        b = b.clone()
     return w, b
 
 
@@ -195,6 +208,7 @@ class _Conv:
     def __init__(self, conv, bn, relu, dtype, fused):
         w, b = _fold(conv, bn)
         self.name = (_issuer.names or {}).get(id(conv), type(conv).__name__)
+        self.bn_name = (_issuer.names or {}).get(id(bn)) if isinstance(bn, _BatchNorm) else None     # refresh() finds the pair again by name
         self.w = w.to(dtype).contiguous(memory_format=torch.channels_last)
         self.b32 = b.float().contiguous()
         self.b = b.to(dtype)
@@ -303,14 +317,21 @@ class _Conv:
         `other`, the junction's second layer, along K]), packed on first use (the warm-up passes, never inside graph capture)."""
         if self.w_tiled is None:
             assert not torch.cuda.is_current_stream_capturing(), 'weights must be tiled before graph capture'
-            lib = _lib.load()
-            cout, src = self.w.shape[0], self.w
-            if order == 2:
-                src = src.reshape(cout, -1) if other is None else torch.cat([src.reshape(cout, -1), other.w.reshape(cout, -1)], 1)
-                src = src.contiguous()
-            self.w_tiled = torch.empty(src.numel(), dtype=src.dtype, device=src.device)
-            _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(src), src.shape[1], cout, order, _lib.ptr(self.w_tiled), _lib.stream_ptr(src.device)), lib)
+            self.w_tiled_src = (order, other)
+            self.pack_tiled()
         return self.w_tiled
+
+    def pack_tiled(self):
+        """(Re-)pack w_tiled from the current weights, into its existing storage when it has one (refresh: the graphs keep the address)."""
+        order, other = self.w_tiled_src
+        lib = _lib.load()
+        cout, src = self.w.shape[0], self.w
+        if order == 2:
+            src = src.reshape(cout, -1) if other is None else torch.cat([src.reshape(cout, -1), other.w.reshape(cout, -1)], 1)
+            src = src.contiguous()
+        if self.w_tiled is None:
+            self.w_tiled = torch.empty(src.numel(), dtype=src.dtype, device=src.device)
+        _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(src), src.shape[1], cout, order, _lib.ptr(self.w_tiled), _lib.stream_ptr(src.device)), lib)
 
     def band_pack(self, device, proj=None):
         """The layer's weights (+ the projection's) in og_conv_band_*'s fragment order, packed once (never inside graph capture)."""
@@ -319,14 +340,19 @@ class _Conv:
         assert self.w_band is None or self.w_band_c2 == c2, 'band_pack: layer already packed with a different projection'
         if self.w_band is None:
             assert not torch.cuda.is_current_stream_capturing(), 'weights must be packed before graph capture'
-            lib = _lib.load()
-            cout, c = self.w.shape[0], self.w.shape[1]
-            self.w_band_c2 = c2
-            self.w_band = torch.empty(cout * (9 * c + c2), dtype=self.w.dtype, device=self.w.device)
-            w2 = proj.w.reshape(cout, c2).contiguous() if proj is not None else None
-            _lib.check(lib.og_conv_band_pack_w16(_lib.ptr(self.w), _lib.ptr(w2) if w2 is not None else None, c, cout, c2,
-                                                 _lib.ptr(self.w_band), _lib.stream_ptr(device)), lib)
+            self.w_band_c2, self.w_band_proj = c2, proj
+            self.pack_band(device)
         return self.w_band
+
+    def pack_band(self, device):
+        """(Re-)pack w_band from the current weights (+ the projection's), into its existing storage when it has one (refresh)."""
+        lib = _lib.load()
+        cout, c, c2, proj = self.w.shape[0], self.w.shape[1], self.w_band_c2, self.w_band_proj
+        if self.w_band is None:
+            self.w_band = torch.empty(cout * (9 * c + c2), dtype=self.w.dtype, device=self.w.device)
+        w2 = proj.w.reshape(cout, c2).contiguous() if proj is not None else None
+        _lib.check(lib.og_conv_band_pack_w16(_lib.ptr(self.w), _lib.ptr(w2) if w2 is not None else None, c, cout, c2,
+                                             _lib.ptr(self.w_band), _lib.stream_ptr(device)), lib)
 
     def warm_next(self, lib):
         """og_conv_next_weights_hint for the launch that follows: the packed weights of the layer after this one, in whichever layout
@@ -608,7 +634,9 @@ class _Layers:
 
     def __init__(self, model, dtype, device, stage, fused):
         self.heads_b, self.head_channels = None, None
-        self.stage = stage
+        self.stage, self.dtype, self.device, self.fused = stage, dtype, device, fused
+        self.module = weakref.ref(model)      # the module whose CURRENT weights the bundle holds (moved by refresh)
+        self._fold_table, self._fold_slots, self._finalizer = None, [], None
         # the caller's module is only read: weights are folded from it onto the engine's device (no .to(), no .eval())
         _issuer.build_device = device
         _issuer.names = {id(m): n for n, m in model.named_modules()}
@@ -660,6 +688,101 @@ class _Layers:
             self.heads_w = w.contiguous(memory_format=torch.channels_last)
             self.heads_b = b.contiguous()
 
+    # ---- refresh: the same buffers, new contents ------------------------------------------------------------------------------
+    def _residuals(self):
+        def level(lv):
+            for seq in (lv.up1, lv.low1, lv.low3):
+                yield from seq
+            yield from (level(lv.low2) if isinstance(lv.low2, _Level) else lv.low2)
+        yield self.pre[1]
+        for lv in self.kps:
+            yield from level(lv)
+        yield from self.inters
+
+    def _convs(self):
+        """Every (_Conv, partner): partner = the _Conv whose folded bias _Residual / _build added to this one's, or None."""
+        yield self.pre[0], None
+        for r in self._residuals():
+            yield r.c1, None
+            if r.skip is not None:
+                yield r.skip, None
+            yield r.c2, r.skip
+        for c in self.cnvs:
+            yield c, None
+        for a_, b_ in zip(self.inters_, self.cnvs_):
+            yield b_, None
+            yield a_, b_
+        for h in (self.hm, self.off, self.scale, self.jitter):
+            if h is not None:
+                yield h, None
+
+    def refresh(self, model, events=None):
+        """Fold `model`'s current weights into the bundle's EXISTING tensors: w, b32, b of every _Conv (one og_fold_bn_w16 launch on a
+        fused bundle, torch's _fold copied in place otherwise), then every derived image that exists.  No tensor changes address.  The
+        caller (InferenceEngine.refresh) brackets this with device synchronisation.  events: a list that receives the (start, end)
+        HIP timing events round the fold launch (tools/engine_refresh_bench.py)."""
+        mods = dict(model.named_modules())
+        convs = list(self._convs())
+        pairs = []
+        for c, _ in convs:
+            if c.name not in mods or (c.bn_name is not None and c.bn_name not in mods):
+                raise ValueError(f'refresh: the module has no layer {c.name!r}: not the architecture this engine was built from')
+            conv, bn = mods[c.name], mods[c.bn_name] if c.bn_name is not None else None
+            if tuple(conv.weight.shape) != tuple(c.w.shape) or (bn is not None and not isinstance(bn, _BatchNorm)):
+                raise ValueError(f'refresh: layer {c.name!r} is {tuple(conv.weight.shape)} in the module, {tuple(c.w.shape)} in the engine')
+            pairs.append((conv, bn))
+        with torch.no_grad():
+            if self.fused:
+                from . import fold
+                fold.fold_bundle(self, convs, pairs, events)
+            else:
+                self._fold_torch(convs, pairs)
+            self._rederive()
+
+    def _fold_torch(self, convs, pairs):
+        _issuer.build_device = self.device
+        try:
+            folded = {}
+            for (c, partner), (conv, bn) in zip(convs, pairs):
+                w, b = _fold(conv, bn)
+                folded[id(c)] = b = b.float()
+                if partner is not None:
+                    b = b + folded[id(partner)]          # _convs yields the partner first
+                c.w.copy_(w.to(self.dtype))
+                c.b32.copy_(b)
+                c.b.copy_(b.to(self.dtype))
+        finally:
+            _issuer.build_device = None
+
+    def _rederive(self):
+        """Every derived weight image that exists, recomputed from the (new) w / b32 into its own storage: w_cat (= c2.w_alt),
+        stem_w, heads_w / heads_b, heads_tiled, and each layer's w_tiled / w_band.  Images not made yet stay None."""
+        dtype = self.dtype
+        for r in self._residuals():
+            if r.w_cat is not None:
+                cout = r.c2.w.shape[0]
+                r.w_cat.copy_(torch.cat([r.c2.w.permute(0, 2, 3, 1).reshape(cout, -1), r.skip.w.reshape(cout, -1)], 1))
+        if self.stem_w is not None:
+            self.stem_w.zero_()
+            self.stem_w[:, :, :7, :3] = self.pre[0].w.float().permute(0, 2, 3, 1).to(dtype)
+        if self.heads_w is not None:
+            parts = [h for h in (self.hm, self.off, self.scale, self.jitter) if h is not None]
+            n = sum(self.head_channels)
+            self.heads_w[:n].copy_(torch.cat([h.w for h in parts], 0))
+            self.heads_b[:n].copy_(torch.cat([h.b32 for h in parts], 0))
+            if getattr(self, 'heads_tiled', None) is not None:
+                packed, bpad, cout = self.heads_tiled
+                lib, c = _lib.load(), self.heads_w.shape[1]
+                wpad = torch.zeros((cout, c), dtype=self.heads_w.dtype, device=self.heads_w.device)
+                wpad[:self.heads_w.shape[0]] = self.heads_w.reshape(self.heads_w.shape[0], -1)
+                bpad[:self.heads_b.shape[0]] = self.heads_b
+                _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(wpad), c, cout, 3, _lib.ptr(packed), _lib.stream_ptr(wpad.device)), lib)
+        for c, _ in self._convs():
+            if c.w_tiled is not None:
+                c.pack_tiled()
+            if c.w_band is not None:
+                c.pack_band(self.device)
+
 
 _layer_cache = {}       # key -> (weak reference to the module, _Layers); at most _LAYER_CACHE_MAX entries, oldest dropped first
 _LAYER_CACHE_MAX = 2
@@ -705,9 +828,24 @@ def _shared_layers(model, dtype, device, stage, fused):
         hit = (weakref.ref(model), _Layers(model, dtype, device, stage, fused))
         while len(_layer_cache) >= _LAYER_CACHE_MAX:
             _layer_cache.pop(next(iter(_layer_cache)))
-        weakref.finalize(model, _layer_cache.pop, key, None)     # the folded weights (~0.75 GB) go when the module goes
+        hit[1]._finalizer = weakref.finalize(model, _layer_cache.pop, key, None)     # the folded weights (~0.75 GB) go when the module goes
     _layer_cache[key] = hit      # (re-)inserted last: most recently used
     return hit[1]
+
+
+def _recache(layers, model):
+    """A refreshed bundle is filed under the signature of the weights it now holds: the entry it had (older weights, maybe another
+    module) goes, so a module put back to those weights is folded afresh."""
+    for key in [k for k, v in _layer_cache.items() if v[1] is layers]:
+        del _layer_cache[key]
+    key = (id(model), _model_signature(model), layers.dtype, str(layers.device), layers.stage, layers.fused)
+    while len(_layer_cache) >= _LAYER_CACHE_MAX:
+        _layer_cache.pop(next(iter(_layer_cache)))
+    if layers._finalizer is not None:     # the one of the entry that has just gone
+        layers._finalizer.detach()
+    layers._finalizer = weakref.finalize(model, _layer_cache.pop, key, None)
+    _layer_cache[key] = (weakref.ref(model), layers)
+    layers.module = weakref.ref(model)
 
 
 class InferenceEngine:
@@ -741,7 +879,7 @@ class InferenceEngine:
         # share them (evaluate.run_images builds one engine per input shape, --fixed-height: one per width)
         # like = an engine the caller built for this very module a moment ago (evaluate.run_images: one per shape and lane): its
         # bundle is taken as it is, without the 0.2 s look at every weight that decides whether a cached bundle is still current
-        if (like is not None and like._model() is model and like.dtype == dtype and like.device == self.device
+        if (like is not None and like._model() is model and like._layers.module() is model and like.dtype == dtype and like.device == self.device
                 and like.stage == self.stage):
             self._layers = like._layers
         else:
@@ -845,6 +983,31 @@ class InferenceEngine:
         self._graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self._graph):
             self._out = self._forward(self._static_in)
+
+    def refresh(self, model=None):
+        """Bring the engine -- and every engine that shares its weight bundle: the other input shapes, both lanes -- to the CURRENT
+        weights of `model` (default: the module the bundle was last built or refreshed from; a DistributedDataParallel wrapper is
+        unwrapped; another module must have the same layers and shapes).  Every persistent weight buffer is rewritten IN PLACE: one
+        og_fold_bn_w16 launch folds BatchNorm (running statistics, whatever the train / eval flag) into w / b32 / b of every layer,
+        the packed images that exist are packed again into their storage, so the captured graphs replay the new weights without
+        being captured again and nothing is allocated for good.  NOT part of a step: it waits for the device before it writes (a
+        replay in flight still reads the old weights) and after it has written -- a once-per-epoch call.  The bundle's cache entry
+        moves to the module's new signature: a later InferenceEngine(model, ...) reuses the refreshed bundle."""
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+            model = model.module
+        if model is None:
+            model = self._layers.module()
+            if model is None:
+                raise ValueError('refresh: the module this engine was built from no longer exists; pass one')
+        cuda = self.device.type == 'cuda'
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        self._layers.refresh(model)
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        self._model = weakref.ref(model)
+        _recache(self._layers, model)
+        return self
 
     @torch.no_grad()
     def forward_raw(self, images):
