@@ -3,6 +3,9 @@ _summarizeKps) restated with straight Python loops on Python floats (IEEE double
 Shares no code with offsetguided_amd/cocoeval.py: the constants are written out again here.
 
 build_case() -> (ground_truth, results, image_ids, notes); restate(ground_truth, results, image_ids) -> dict of numpy arrays.
+match_rows(...) is the matching rule of one image on its own (restate calls it; tests/oks_match_cases.py feeds it hand-written OKS
+blocks).  build_oks_table() / oks_table_reference() are the directed table for og_oks_matrix_f64, build_perfect_case() a set of
+detections that coincide with their ground truths.
 """
 import math
 
@@ -43,6 +46,44 @@ def oks_pair(det, gt, area, bbox, sigmas=SIGMAS):
     return total / n
 
 
+def match_rows(oks_rows, gt_area, gt_ignore, gt_crowd, det_area, area_ranges, thresholds):
+    """evaluateImg's matching of one image for every (area range, threshold).  oks_rows: d rows of g values (detections in score
+    order); gt_ignore: iscrowd or num_keypoints == 0, before the area range is applied.
+    -> (dt_match (A,T,d) int32: 1 + the matched ground truth's index or 0, dt_ignore (A,T,d) uint8, gt_ignore_a (A,g) uint8)."""
+    n_d, n_g = len(det_area), len(gt_area)
+    rows = [[float(v) for v in row] for row in oks_rows]
+    assert len(rows) == n_d and all(len(row) == n_g for row in rows) and len(gt_ignore) == len(gt_crowd) == n_g
+    area, d_area = [float(v) for v in gt_area], [float(v) for v in det_area]
+    ignore, crowd = [bool(v) for v in gt_ignore], [bool(v) for v in gt_crowd]
+    A, T = len(area_ranges), len(thresholds)
+    dt_match, dt_ignore = np.zeros((A, T, n_d), np.int32), np.zeros((A, T, n_d), np.uint8)
+    gt_ignore_a = np.zeros((A, n_g), np.uint8)
+    for a, (lo, hi) in enumerate(area_ranges):
+        lo, hi = float(lo), float(hi)
+        for t, thr in enumerate(thresholds):
+            gig = [ignore[j] or area[j] < lo or area[j] > hi for j in range(n_g)]
+            visit = [j for j in range(n_g) if not gig[j]] + [j for j in range(n_g) if gig[j]]
+            taken = [False] * n_g
+            for d in range(n_d):
+                best, m = min(float(thr), 1 - 1e-10), -1
+                for j in visit:
+                    if taken[j] and not crowd[j]:
+                        continue
+                    if m > -1 and not gig[m] and gig[j]:
+                        break
+                    if rows[d][j] < best:
+                        continue
+                    best, m = rows[d][j], j
+                if m > -1:
+                    dt_match[a, t, d], dt_ignore[a, t, d] = m + 1, gig[m]
+                    taken[m] = True
+                elif d_area[d] < lo or d_area[d] > hi:
+                    dt_ignore[a, t, d] = 1
+            for j in range(n_g):
+                gt_ignore_a[a, j] = gig[j]
+    return dt_match, dt_ignore, gt_ignore_a
+
+
 def restate(ground_truth, results, image_ids, sigmas=SIGMAS):
     """-> {'oks' (packed, image after image, row-major d_i x g_i), 'det_off', 'gt_off', 'dt_match' (A,T,D), 'dt_ignore' (A,T,D),
     'gt_ignore_a' (A,G), 'precision' (T,R,A), 'recall' (T,A), 'stats' (10)}.  image_ids must not repeat."""
@@ -73,32 +114,12 @@ def restate(ground_truth, results, image_ids, sigmas=SIGMAS):
     D, G = sum(len(im['score']) for im in images), sum(len(im['gt']['area']) for im in images)
     dt_match, dt_ignore = np.zeros((A, T, D), np.int32), np.zeros((A, T, D), np.uint8)
     gt_ignore_a = np.zeros((A, G), np.uint8)
-    for a, (lo, hi) in enumerate(AREA_RANGES):
-        for t, thr in enumerate(IOU_THRS):
-            d0 = g0 = 0
-            for im in images:
-                g, n_d, n_g = im['gt'], len(im['score']), len(im['gt']['area'])
-                gig = [g['ignore'][j] or g['area'][j] < lo or g['area'][j] > hi for j in range(n_g)]
-                visit = [j for j in range(n_g) if not gig[j]] + [j for j in range(n_g) if gig[j]]
-                taken = [False] * n_g
-                for d in range(n_d):
-                    best, m = min(float(thr), 1 - 1e-10), -1
-                    for j in visit:
-                        if taken[j] and not g['crowd'][j]:
-                            continue
-                        if m > -1 and not gig[m] and gig[j]:
-                            break
-                        if im['oks'][d][j] < best:
-                            continue
-                        best, m = im['oks'][d][j], j
-                    if m > -1:
-                        dt_match[a, t, d0 + d], dt_ignore[a, t, d0 + d] = m + 1, gig[m]
-                        taken[m] = True
-                    elif im['area'][d] < lo or im['area'][d] > hi:
-                        dt_ignore[a, t, d0 + d] = 1
-                for j in range(n_g):
-                    gt_ignore_a[a, g0 + j] = gig[j]
-                d0, g0 = d0 + n_d, g0 + n_g
+    d0 = g0 = 0
+    for im in images:
+        g, n_d, n_g = im['gt'], len(im['score']), len(im['gt']['area'])
+        dt_match[:, :, d0:d0 + n_d], dt_ignore[:, :, d0:d0 + n_d], gt_ignore_a[:, g0:g0 + n_g] = match_rows(
+            im['oks'], g['area'], g['ignore'], g['crowd'], im['area'], AREA_RANGES, IOU_THRS)
+        d0, g0 = d0 + n_d, g0 + n_g
     scores = [s for im in images for s in im['score']]
     order = sorted(range(D), key=lambda j: -scores[j])
     precision, recall = -np.ones((T, R, A)), -np.ones((T, A))
@@ -269,3 +290,85 @@ def check_gaps(ref, image_ids, notes):
                     else:
                         assert abs(vals[j] - vals[k]) >= GAP, (image_ids[i], j, k, vals[j], vals[k])
     assert row == len(ref['rows'])
+
+
+# ---- the directed table for og_oks_matrix_f64 ----
+SIGMA_SETS = {'coco': SIGMAS, 'flat': [0.05] * K, 'one_tiny': SIGMAS[:3] + [1e-3] + SIGMAS[4:]}
+BBOX = [100.0, 100.0, 40.0, 60.0]            # the doubled box of the bbox branch: x in [60, 180], y in [40, 220]
+
+
+def build_oks_table(extra=False, seed=5):
+    """Images for one og_oks_matrix_f64 launch: [(dets (d,17,3), gts (g,17,3), area (g,), bbox (g,4))] and notes {name: image index}.
+    256 pairs -- one full block -- or 257 with `extra` (one more 1 x 1 image); images without pairs stand first (detections only), in
+    the middle (ground truths only) and last (detections only).
+      ordinary   6 x 5: ground truth 2 is ground truth 1 with every v = 2 written as v = 1
+      exact      3 x 3: ground truths P (area 5000), P (area 0), P with joints hidden (area 0); detections P, P + 1 px, P + 10^4 px
+      bbox       6 x 2: ground truth 0 has no annotated joint and BBOX; detections: all joints inside the doubled box, all on its edges,
+                 then 4 / 8 / 12 / 17 joints 3 px beyond its left / right / top / bottom side
+      underflow  1 x 1: one annotated joint, 62.4 px off at area 1000: e = 720 under COCO's sigma, exp(-e) is subnormal
+      filler     3 x 68 ordinary pairs"""
+    rs = np.random.RandomState(seed)
+    c = (150.0, 150.0)
+
+    def img(dets, rows):
+        g = _gt(rows)
+        return (np.array(dets, np.float64).reshape(-1, K, 3), g['keypoints'], g['area'], g['bbox'])
+
+    none = np.zeros((0, K, 3))
+    p = [_hide(rs, _person(rs, c, 20)) for _ in range(4)]
+    twin = p[1].copy()
+    twin[twin[:, 2] > 0, 2] = 1.0
+    ordinary = img([_near(rs, p[j % 4], 1.0 + j) for j in range(6)],
+                   [(p[0], 3000.0, 0), (p[1], 6000.0, 0), (twin, 6000.0, 0), (p[2], 12000.0, 0), (p[3], 25000.0, 0)])
+    P = _person(rs, c, 5)
+    off1, far = P.copy(), P.copy()
+    off1[:, 0] += 1.0
+    far[:, :2] += 1e4
+    exact = img([P.copy(), off1, far], [(P, 5000.0, 0), (P.copy(), 0.0, 0), (_hide(rs, P), 0.0, 0)])
+    x0, x1, y0, y1 = 60.0, 180.0, 40.0, 220.0
+    inside = np.stack([rs.uniform(x0 + 1, x1 - 1, K), rs.uniform(y0 + 1, y1 - 1, K), np.full(K, 2.0)], 1)
+    edges = inside.copy()
+    for k in range(K):
+        edges[k, k % 2] = (x0, y0, x1, y1)[k % 4]                      # x = 60, y = 40, x = 180, y = 220 in turn
+    edges[16, :2] = [x0, y1]                                            # and a corner
+    beyond = []
+    for n, col, value in ((4, 0, x0 - 3.0), (8, 0, x1 + 3.0), (12, 1, y0 - 3.0), (17, 1, y1 + 3.0)):
+        kp = inside.copy()
+        kp[:n, col] = value
+        beyond.append(kp)
+    bbox = img([inside, edges] + beyond, [(np.zeros((K, 3)), 4000.0, 0), (_hide(rs, _person(rs, c, 20)), 8000.0, 0)])
+    bbox[3][0] = BBOX
+    one = np.zeros((K, 3))
+    one[0] = [100.0, 100.0, 2.0]
+    off = one.copy()
+    off[0, 0] += 62.4
+    underflow = img([off], [(one, 1000.0, 0)])
+    f = [_hide(rs, _person(rs, c, 25)) for _ in range(68)]
+    filler = img([_near(rs, f[j], 3.0) for j in range(3)], [(kp, float(rs.uniform(2000.0, 30000.0)), 0) for kp in f])
+    q = _hide(rs, _person(rs, c, 10))
+    images = [(np.array([_person(rs, c, 10), _person(rs, c, 10)]), none, np.zeros(0), np.zeros((0, 4))), ordinary, exact,
+              (none, ) + img([], [(kp, 5000.0, 0) for kp in f[:3]])[1:], bbox, underflow, filler]
+    notes = {'ordinary': 1, 'exact': 2, 'bbox': 4, 'underflow': 5, 'filler': 6}
+    if extra:
+        images.append(img([_near(rs, q, 2.0)], [(q, 7000.0, 0)]))
+        notes['extra'] = 7
+    images.append((np.array([_person(rs, c, 10)]), none, np.zeros(0), np.zeros((0, 4))))
+    return images, notes
+
+
+def oks_table_reference(images, sigmas=SIGMAS):
+    """-> the packed values (image after image, row-major d_i x g_i) from oks_pair."""
+    return np.array([oks_pair(d, gts[j], area[j], bbox[j], sigmas) for dets, gts, area, bbox in images for d in dets
+                     for j in range(len(gts))], np.float64)
+
+
+def build_perfect_case(seed=6):
+    """Two images, three ground truths each (one of area 0), far apart; one detection per ground truth with its very coordinates: every
+    matching OKS is exactly 1.0.  -> (ground_truth, results, image_ids)."""
+    rs = np.random.RandomState(seed)
+    gt, res = {}, []
+    for image_id, areas in ((31, (5000.0, 0.0, 20000.0)), (37, (900.0, 7000.0, 0.0))):
+        people = [_hide(rs, _person(rs, (150.0 + 300.0 * j, 150.0), 5)) for j in range(3)]
+        gt[image_id] = _gt([(kp, a, 0) for kp, a in zip(people, areas)])
+        res += _results(image_id, [(kp, float(rs.uniform(0.1, 0.9))) for kp in people])
+    return gt, res, [31, 37]
