@@ -423,7 +423,12 @@ int og_conv1x1_heads_bf16(const void *x, int C, const void *w_packed, const floa
  * (device memory, 64 B per workgroup); NULL switches it off. */
 /* ---- the same entry points for fp16 activations / weights (the reference evaluates in fp16 through apex O2,
  * evaluate.py:92,198-201): v_mfma_f32_16x16x32_f16 instead of ..._bf16, fp32 accumulation, identical layouts, arguments,
- * workspaces (og_conv*_workspace_bytes) and error behaviour; models.InferenceEngine(dtype=torch.float16). ---- */
+ * workspaces (og_conv*_workspace_bytes) and error behaviour; models.InferenceEngine(dtype=torch.float16).
+ * At the ends of the fp16 range -- observed on gfx950 on the 29 small shapes of tests/test_gpu_conv_exact.py (*_range) and the directed
+ * cases of tests/test_gpu_range_glue.py, an observation those tests hold, not a guarantee beyond them: subnormal fp16 weights and
+ * activations went through the MFMA, the stem's input conversion, the phase images, skip / up operands and the weight packers
+ * unflushed; outputs below 2^-14 were rounded to nearest even on the subnormal grid; outputs that round beyond 65504 came out as
+ * +-inf, not clamped; og_conv1x1_heads_f16 wrote the fp32 value unrounded. ---- */
 int og_bias_act_f16(void *x, const float *bias, const void *skip, long pixels, int channels, int relu, void *stream);
 int og_upsample2_add_f16(void *up, const void *low, long n, int H, int W, int channels, void *stream);
 int og_nchw_f32_to_nhwc_f16(const float *src, void *dst, long N, int C, int H, int W, void *stream);

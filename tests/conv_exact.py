@@ -8,6 +8,8 @@ exact in fp32.  What is left is the one final rounding to the output type, which
 
 The reference is a plain fp64 sum over the k*k taps of a shifted NHWC slice times that tap's (Cin, Cout) matrix; it never calls
 torch's convolution (tests/test_conv_exact_cpu.py holds it to F.conv2d in fp64, bit for bit)."""
+import math
+
 import torch
 
 X_MAX, W_MAX = 3, 2                      # integer activations in [-3, 3], integer weights in [-2, 2]
@@ -15,6 +17,34 @@ BIAS_GRID, BIAS_MAX = 64, 4              # bias = k / 64, k odd, |bias| <= 4 (fp
 RES_GRID, RES_MAX = 8, 8                 # residual / up = k / 8, |.| <= 8: exact in bf16 (8 significant bits) and fp16 alike
 SUM_LIMIT = 1 << 15
 MANTISSA_BITS = {torch.bfloat16: 8, torch.float16: 11}      # significant bits, the hidden one included
+MIN_ULP_EXP = {torch.bfloat16: -133, torch.float16: -24}    # log2 of the spacing of the subnormals
+F16_MIN_NORMAL, F16_MAX = 2.0 ** -14, 65504.0
+
+# Regimes: powers of two (a, b) on the operands.  x, x2 are multiplied by 2^a, w, w2 by 2^b, bias, res and up by 2^t, t = a + b:
+# every product and every partial sum of the argument above is the old one times 2^t -- still exact -- but the operands or the
+# result now lie at the ends of the 16-bit type's range.  fp16: w_sub (every non-zero weight +-2^-24 or +-2^-23, a subnormal),
+# x_sub (every non-zero activation a subnormal), out_sub (normal operands; |v| < 128 rounds into the subnormal range, spacing
+# 2^-24 = 2^-3 in units of v), overflow (exponents from the case's K, overflow_exponents).  bf16: far (operand exponents far outside
+# fp16's range).
+REGIMES = {'w_sub': (10, -24), 'x_sub': (-24, 10), 'out_sub': (-11, -10), 'far': (30, -40)}
+REGIME_DTYPE = {'w_sub': torch.float16, 'x_sub': torch.float16, 'out_sub': torch.float16, 'overflow': torch.float16,
+                'far': torch.bfloat16}
+PRODUCT_VARIANCE = 19.5                  # of one product x * w under _ints: E[x^2] E[w^2] = 6.5 * 3
+OUT_SUB_BIAS_GRID = 32
+
+
+def overflow_exponents(k_total, shift=0, x_fp32=False):
+    """(a, b) of the 'overflow' regime from K alone: s = ceil(log2(65504 / (2 sqrt(19.5 K)))) (+ shift), so that 65504 lies between
+    one and two standard deviations of the scaled sum and a few per cent of the outputs lie beyond it; a = s // 2, b = s - s // 2.
+    x_fp32 (the stem: its images are fp32 and are not scaled): (0, s)."""
+    s = math.ceil(math.log2(F16_MAX / (2 * math.sqrt(PRODUCT_VARIANCE * k_total)))) + shift
+    return (0, s) if x_fp32 else (s // 2, s - s // 2)
+
+
+def regime_exponents(regime, k_total=None, shift=0, x_fp32=False):
+    if regime is None:
+        return 0, 0
+    return overflow_exponents(k_total, shift, x_fp32) if regime == 'overflow' else REGIMES[regime]
 
 
 def worst_case_sum(k_total):
@@ -51,27 +81,52 @@ def _odd_grid(g, shape, grid, lim):
     return (torch.randint(-lim * grid // 2, lim * grid // 2, shape, generator=g).float() * 2 + 1) / grid
 
 
-def exact_operands(seed, n, h, w, cin, cout, k=3, stride=1, second=None, up=False, bias_grid=BIAS_GRID):
+def exact_operands(seed, n, h, w, cin, cout, k=3, stride=1, second=None, up=False, bias_grid=BIAS_GRID, regime=None, shift=0,
+                   x_fp32=False):
     """fp32 CPU tensors (NCHW) for one convolution case: x (n,cin,h,w), w (cout,cin,k,k), bias (cout,), res (n,cout,ho,wo) with
     ho = (h + 2 (k // 2) - k) // stride + 1; with second = (h2, w2, cin2): x2 (n,cin2,h2,w2) and w2 (cout,cin2), the operand
     concatenated along K (the residual's 1x1 projection, the junction's second input); with up: up (n,cout,2 ho,2 wo).
     x2 lies on the 2^-3 grid like the residual but within the ACTIVATION range |x2| <= 3: the worst-case sum 6 K + 4 + 8 counts
     every one of the K products, the second input's included, as at most 3 * 2.
     bias_grid: 64 everywhere but in the sensitivity test (every k / 64 with |k| <= 256 has 8 significant bits and is exact in bf16
-    and fp16 alike; a bias that a 16-bit rounding would change needs a finer grid, and the precondition then counts its bits)."""
+    and fp16 alike; a bias that a 16-bit rounding would change needs a finer grid, and the precondition then counts its bits).
+    regime: None (the tensors above, unscaled) or a name of REGIMES / 'overflow' (shift, x_fp32: overflow_exponents): x, x2 times
+    2^a, w, w2 times 2^b, bias, res, up times 2^(a + b).  The draws are those of the default regime but for two operands that
+    would fall off the type's grid or miss the regime's point:
+      x_sub:    x2 is drawn as integers in [-3, 3] (k / 8 * 2^-24 is no fp16 number);
+      out_sub:  the bias is drawn on the plain 2^-5 grid (_grid, any numerator).  The subnormal spacing is 2^-3 in units of v: an
+                odd-numerator k / 64 never lands on a tie, and on the 2^-4 grid every inexact value IS a tie (no other rounding
+                could occur below |v| = 256); k / 32 gives exact values, ties (k = 2 mod 4) and roundings off a tie (k odd).
+    res and up stay on the 2^-3 grid: at t = -21 (out_sub) that is k 2^-24, at t = -14 k 2^-17 -- fp16 numbers by construction.
+    Asserted from the tensors themselves: every 16-bit operand survives the regime's type unchanged."""
     cin2 = second[2] if second is not None else 0
-    check_precondition(k * k * cin + cin2, bias_grid)
+    k_total = k * k * cin + cin2
+    if regime == 'out_sub':
+        assert bias_grid == BIAS_GRID
+        bias_grid = OUT_SUB_BIAS_GRID
+    check_precondition(k_total, bias_grid)
     g = torch.Generator(device='cpu').manual_seed(seed)
     pad = k // 2
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    draw_bias = _grid if regime == 'out_sub' else _odd_grid
     ops = {'x': _ints(g, (n, cin, h, w), X_MAX), 'w': _ints(g, (cout, cin, k, k), W_MAX),
-           'bias': _odd_grid(g, (cout,), bias_grid, BIAS_MAX), 'res': _grid(g, (n, cout, ho, wo), RES_GRID, RES_MAX)}
+           'bias': draw_bias(g, (cout,), bias_grid, BIAS_MAX), 'res': _grid(g, (n, cout, ho, wo), RES_GRID, RES_MAX)}
     if second is not None:
         h2, w2, _ = second
-        ops['x2'] = _grid(g, (n, cin2, h2, w2), RES_GRID, X_MAX)
+        ops['x2'] = _grid(g, (n, cin2, h2, w2), 1 if regime == 'x_sub' else RES_GRID, X_MAX)
         ops['w2'] = _ints(g, (cout, cin2), W_MAX)
     if up:
         ops['up'] = _grid(g, (n, cout, 2 * ho, 2 * wo), RES_GRID, RES_MAX)
+    if regime is None:
+        return ops
+    a, b = regime_exponents(regime, k_total, shift, x_fp32)
+    dtype = REGIME_DTYPE[regime]
+    for name, t in ops.items():
+        e = a if name in ('x', 'x2') else b if name in ('w', 'w2') else a + b
+        ops[name] = torch.ldexp(t, torch.tensor(e))
+        assert torch.equal(ops[name].double(), torch.ldexp(t.double(), torch.tensor(e))) and bool(ops[name].isfinite().all()), name
+        if name != 'bias':                                        # (fp32 on the device; the stem's fp32 images must convert exactly too)
+            assert torch.equal(ops[name].to(dtype).float(), ops[name]), f'{regime}: {name} does not survive {dtype}'
     return ops
 
 
@@ -123,16 +178,64 @@ def exact_reference(x, w, bias=None, res=None, relu=False, stride=1, x2=None, w2
     return out
 
 
+def _ulp_scaled(v64, dtype):
+    """|v| in units of the spacing of `dtype` at v (the subnormal spacing below the smallest normal)."""
+    _, e = torch.frexp(v64.abs())                                   # |v| = m 2^e, m in [0.5, 1)
+    ue = (e - MANTISSA_BITS[dtype]).clamp(min=MIN_ULP_EXP[dtype])
+    return v64.abs() * torch.pow(torch.tensor(2.0, dtype=torch.float64, device=v64.device), -ue.double())   # (2^133 needs fp64)
+
+
 def rounding_coverage(v64, dtype, expected=None):
     """(elements whose expected value differs from the unrounded fp64 value v64, exact ties of the rounding of v64 to `dtype`,
     elements).  expected: default the one rounding of v64; og_conv3x3_tiled_up2_* passes its twice-rounded expectation next to the
     never-rounded up + nearest2x(act(conv + bias + skip))."""
     r = (v64.float().to(dtype) if expected is None else expected).double()
     changed = int((r != v64).sum())
-    m, _ = torch.frexp(v64.abs())                                   # |v| = m 2^e, m in [0.5, 1)
-    scaled = m * float(1 << MANTISSA_BITS[dtype])
+    scaled = _ulp_scaled(v64, dtype)
     ties = int(((scaled - scaled.floor()) == 0.5).sum())            # exactly half a unit in the last place: RNE decides
     return changed, ties, v64.numel()
+
+
+RANGE_COUNTS = ('elements', 'subnormals', 'ties', 'nonties', 'infs', 'to_min_normal')
+
+
+def range_coverage(v64, dtype, expected=None):
+    """RANGE_COUNTS of one expected tensor (default: the one rounding of v64) as a dict: its elements; its non-zero elements below
+    the type's smallest normal; exact ties of the rounding of v64; finite elements that the rounding changed off a tie; its
+    infinities; elements that rounded to the smallest normal from below."""
+    r = (v64.float().to(dtype) if expected is None else expected).double()
+    tiny = torch.finfo(dtype).tiny
+    scaled = _ulp_scaled(v64, dtype)
+    tie = (scaled - scaled.floor()) == 0.5
+    counts = (v64.numel(), (r != 0) & (r.abs() < tiny), tie, (r != v64) & r.isfinite() & ~tie, r.isinf(),
+              (r.abs() == tiny) & (v64.abs() < tiny))
+    return {k: int(c if isinstance(c, int) else c.sum()) for k, c in zip(RANGE_COUNTS, counts)}
+
+
+def flush_operand(t):
+    """A 16-bit operand as a unit that flushes fp16 subnormals reads it: zero below 2^-14."""
+    return torch.where(t.abs() < F16_MIN_NORMAL, torch.zeros_like(t), t)
+
+
+def flushed_reference(x, w, bias=None, res=None, relu=False, stride=1, x2=None, w2=None, stride2=1, dtype=torch.float16, up=None):
+    """exact_reference with every 16-bit operand (all but the fp32 bias) of magnitude below 2^-14 set to zero first.  NOT an
+    expectation any kernel is held to: a CPU condition (the regime must tell the two apart) and a count in the failure messages."""
+    f = lambda t: None if t is None else flush_operand(t)      # noqa: E731
+    return exact_reference(f(x), f(w), bias, f(res), relu, stride, f(x2), f(w2), stride2, dtype, f(up))
+
+
+def saturated(expected):
+    """The expectation of a kernel that clamps instead of overflowing: +-inf replaced by +-65504.  As flushed_reference: never a
+    passing expectation."""
+    return torch.where(expected.isinf(), torch.full_like(expected, F16_MAX) * expected.sign(), expected)
+
+
+def describe_kind(got, exp, alternatives):
+    """', of those N equal NAME' for each (name -> tensor) alternative expectation: what kind of failure a mismatch is."""
+    g, e = got.float(), exp.float()
+    bad = (g != e) | (g.isnan() != e.isnan())
+    return ''.join(f'; {int((bad & (g == alt.float().to(g.device))).sum())} of the differing elements equal {name}'
+                   for name, alt in alternatives.items())
 
 
 def describe_mismatch(got, exp):

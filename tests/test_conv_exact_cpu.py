@@ -194,18 +194,18 @@ def test_exact_comparison_sees_what_the_relative_gate_misses(dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------ rounding coverage
-def _family_values(family, shape):
-    """The unrounded fp64 values behind every expected tensor of one GPU case (tests/test_gpu_conv_exact.py: same operands, same
-    epilogue combinations); for up2 the values of the SECOND rounding, per dtype."""
+def _case(family, shape, regime=None):
+    """One GPU case of tests/test_gpu_conv_exact.py on the CPU: (operands, stride, stride2, [(bias?, skip?, relu)] as that file runs
+    them) -- same seed, same regime, same epilogue combinations."""
     import test_gpu_conv_exact as t
-    seed = t._seed(family, shape)
+    k, st, second, st2, up = 3, 1, None, 1, False
     if family == 'stem7x7':
         n, h, w = shape
-        ops = cx.exact_operands(seed, n, h, w, 3, 128, 7, 2)
-        base = cx.exact_sum(ops['x'], ops['w'], stride=2)
-        return lambda dtype: [(cx.apply_epilogue(base, ops['bias'], None, relu), None) for relu in (1, 0)]
-    k, st, second, st2, up = 3, 1, None, 1, False
-    if family == 'conv2d':
+        cin, cout, k, st = 3, 128, 7, 2
+    elif family == 'conv1x1_heads':
+        n, h, w, cin, heads = shape
+        cout, k = sum(heads), 1
+    elif family == 'conv2d':
         n, h, w, cin, cout, k, st = shape
     elif family == 'conv2d_proj':
         n, h, w, cin, cout, h2, w2, c2, st2 = shape
@@ -220,14 +220,19 @@ def _family_values(family, shape):
     else:
         n, h, w, cin, cout = shape
         st, up = (2 if family == 'conv3x3s2_tiled' else 1), family == 'conv3x3_tiled_up2'
-    ops = cx.exact_operands(seed, n, h, w, cin, cout, k, st, second=second, up=up)
+    ops = t._operands(family, shape, regime, n, h, w, cin, cout, k, st, second=second, up=up)
+    combos = {'stem7x7': [(True, False, 1), (True, False, 0)], 'conv1x1_heads': [(True, False, 0)], 'conv1x1_tiled': t.BIAS_SKIP_RELU,
+              'conv2d_proj': [(True, False, 1), (True, False, 0)]}.get(family, [(True, s, r) for s, r in t.SKIP_RELU])
+    return ops, st, st2, combos
+
+
+def _family_values(family, shape):
+    """The unrounded fp64 values behind every expected tensor of one GPU case (tests/test_gpu_conv_exact.py: same operands, same
+    epilogue combinations); for up2 the values of the SECOND rounding, per dtype."""
+    ops, st, st2, combos = _case(family, shape)
     base = cx.exact_sum(ops['x'], ops['w'], stride=st, x2=ops.get('x2'), w2=ops.get('w2'), stride2=st2)
-    if family == 'conv1x1_tiled':
-        vals = [cx.apply_epilogue(base, ops['bias'] if b else None, ops['res'] if s else None, r) for b, s, r in t.BIAS_SKIP_RELU]
-    else:
-        combos = ((False, 1), (False, 0)) if family == 'conv2d_proj' else t.SKIP_RELU
-        vals = [cx.apply_epilogue(base, ops['bias'], ops['res'] if s else None, r) for s, r in combos]
-    if not up:
+    vals = [cx.apply_epilogue(base, ops['bias'] if b else None, ops['res'] if s else None, r) for b, s, r in combos]
+    if 'up' not in ops:
         return lambda dtype: [(v, None) for v in vals]
     x2 = lambda v: v.repeat_interleave(2, 2).repeat_interleave(2, 3)          # noqa: E731
     return lambda dtype: [(ops['up'].double() + x2(v), cx.round_once(ops['up'].double() + x2(cx.round_once(v, dtype).double()), dtype))
@@ -268,3 +273,147 @@ def test_rounding_is_exercised_in_every_family(family):
         changed, ties, total = tot[d]
         print(f'{family} {d}: {changed / total:.1%} of {total} expected outputs rounded, {ties} exact ties, {len(small)} cases')
         assert changed >= 0.25 * total and ties >= 1, (family, d, changed / total, ties)
+
+
+# ------------------------------------------------------------------------------------------------ the ends of the 16-bit range
+# The conditions that keep the range tests of tests/test_gpu_conv_exact.py (RANGE_CASES x RANGE_MODES) from passing vacuously, on
+# the reference alone.  They are conditions on the test data, not measurements of any kernel.
+def _range_ids():
+    import test_gpu_conv_exact as t
+    return [pytest.param(f, *p.values, id=f'{f}-{p.id}') for f in t.RANGE_CASES for p in t._range_params(f)]
+
+
+_range_cache = {}
+# sums of exact_operands(3, 2, 6, 5, 64, 32, 3, 1, second=(6, 5, 64), up=True) as drawn before the function had regimes
+DEFAULT_DRAW_SUMS = [-2.0, 98.0, 5.59375, 238.5, -64.5, 73.0, -538.5]
+
+
+def _range_expectations(family, shape, regime):
+    """(operands, [(combo, never-rounded fp64 value, expected tensor, flushed expectation)]) of one range case, as the GPU file builds
+    them (og_conv1x1_heads_*: fp32 out, expected = the value; up2: two roundings)."""
+    key = (family, shape, regime)
+    if key not in _range_cache:
+        ops, st, st2, combos = _case(family, shape, regime)
+        dtype = cx.REGIME_DTYPE[regime]
+        out = torch.float32 if family == 'conv1x1_heads' else dtype
+        fops = {k: v if k == 'bias' else cx.flush_operand(v) for k, v in ops.items()}
+        base, fbase = (cx.exact_sum(o['x'], o['w'], stride=st, x2=o.get('x2'), w2=o.get('w2'), stride2=st2) for o in (ops, fops))
+        x2 = lambda v: v.repeat_interleave(2, 2).repeat_interleave(2, 3)          # noqa: E731
+        rows = []
+        for b, s, r in combos:
+            v, fv = (cx.apply_epilogue(a, o['bias'] if b else None, o['res'] if s else None, r) for a, o in ((base, ops), (fbase, fops)))
+            exp, fl = cx.round_once(v, out), cx.round_once(fv, out)
+            if 'up' in ops:
+                v, exp, fl = (ops['up'].double() + x2(v), cx.round_once(ops['up'].double() + x2(exp.double()), out),
+                              cx.round_once(fops['up'].double() + x2(fl.double()), out))
+            rows.append(((b, s, r), v, exp, fl))
+        b, s, r = combos[-1]                                                        # flushed_reference is what this test computes by hand
+        assert torch.equal(rows[-1][3], cx.flushed_reference(ops['x'], ops['w'], ops['bias'] if b else None, ops['res'] if s else None, r,
+                                                             st, ops.get('x2'), ops.get('w2'), st2, out, ops.get('up')))
+        _range_cache[key] = ops, rows
+    return _range_cache[key]
+
+
+@pytest.mark.parametrize("regime", ['w_sub', 'x_sub', 'out_sub', 'overflow', 'far'])
+def test_scaled_reference_equals_torch_fp64(regime):
+    """One shape per regime (3x3 stride 1 with a strided second input; the 7x7 stride-2 form): the scaled reference is F.conv2d in
+    fp64 bit for bit, and torch's fp32 result equals it -- scaling by powers of two left every product and partial sum exact."""
+    for n, h, w, cin, cout, k, stride, second in ((1, 4, 3, 8, 8, 3, 1, (7, 6, 16, 2)), (2, 32, 32, 3, 16, 7, 2, None)):
+        st2 = second[3] if second else 1
+        ops = cx.exact_operands(7, n, h, w, cin, cout, k, stride, second=second[:3] if second else None, up=True, regime=regime)
+        ref = _torch_sum(ops, k, stride, st2)
+        got = cx.exact_sum(ops['x'], ops['w'], stride=stride, x2=ops.get('x2'), w2=ops.get('w2'), stride2=st2)
+        assert torch.equal(got, ref) and torch.equal(_torch_sum(ops, k, stride, st2, torch.float32).double(), ref)
+        full = ref + ops['bias'].double().view(1, -1, 1, 1) + ops['res'].double()
+        dtype = cx.REGIME_DTYPE[regime]
+        assert torch.equal(cx.exact_reference(ops['x'], ops['w'], ops['bias'], ops['res'], False, stride, ops.get('x2'), ops.get('w2'),
+                                              st2, dtype=dtype), full.float().to(dtype))
+
+
+def test_default_regime_is_unchanged_and_regimes_scale_it():
+    """regime=None draws what the function drew before it had regimes (the pinned checksum), and w_sub / far are that draw times
+    powers of two."""
+    kw = dict(second=(6, 5, 64), up=True)
+    ops = cx.exact_operands(3, 2, 6, 5, 64, 32, 3, 1, **kw)
+    assert [round(float(ops[k].double().sum()), 6) for k in ('x', 'w', 'bias', 'res', 'x2', 'w2', 'up')] == DEFAULT_DRAW_SUMS
+    for regime in ('w_sub', 'far'):
+        a, b = cx.REGIMES[regime]
+        sc = cx.exact_operands(3, 2, 6, 5, 64, 32, 3, 1, regime=regime, **kw)
+        for name, e in (('x', a), ('x2', a), ('w', b), ('w2', b), ('bias', a + b), ('res', a + b), ('up', a + b)):
+            assert torch.equal(sc[name].double(), ops[name].double() * 2.0 ** e), (regime, name)
+    with pytest.raises(AssertionError, match='does not survive'):                   # the precondition is checked on the tensors themselves
+        cx.exact_operands(3, 1, 4, 4, 64, 8, regime='overflow', shift=6)
+
+
+def test_overflow_exponents_come_from_k_alone():
+    assert [sum(cx.overflow_exponents(k)) for k in (64, 147, 576, 4608)] == [10, 10, 9, 7]
+    assert cx.overflow_exponents(147, x_fp32=True) == (0, 10) and cx.overflow_exponents(576) == (4, 5)
+    assert cx.overflow_exponents(576, shift=-1) == (4, 4)
+
+
+def test_coverage_counts_in_the_subnormal_range():
+    """Spacing 2^-24 below 2^-14: ties and roundings are counted on that spacing, not on 11 bits of the value's own exponent."""
+    u = 2.0 ** -24
+    v = torch.tensor([3 * u, 2.5 * u, 2.25 * u, 0.5 * u, 1023.5 * u, 1023.75 * u, -1023.75 * u, 0.0, 70000.0, 65519.0],
+                     dtype=torch.float64)
+    c = cx.range_coverage(v, torch.float16)
+    assert c == {'elements': 10, 'subnormals': 3, 'ties': 3, 'nonties': 4, 'infs': 1, 'to_min_normal': 3}
+    assert cx.rounding_coverage(v, torch.float16)[:2] == (8, 3)
+    e = v.float().half()
+    assert torch.equal(cx.saturated(e)[-2:], torch.tensor([65504.0, 65504.0]).half()) and torch.equal(cx.saturated(e)[:-2], e[:-2])
+    assert torch.equal(cx.flush_operand(torch.tensor([2.0 ** -14, -2.0 ** -15, 3 * u, 0.0])), torch.tensor([2.0 ** -14, 0.0, 0.0, 0.0]))
+    got = e.clone()
+    got[0], got[8] = 0.0, 65504.0
+    kinds = {'A': torch.zeros(1, 1, 1, 10), 'B': cx.saturated(e).view(1, 1, 1, -1)}
+    assert cx.describe_kind(got.view(1, 1, 1, -1), e.view(1, 1, 1, -1), kinds) \
+        == '; 1 of the differing elements equal A; 1 of the differing elements equal B'
+
+
+@pytest.mark.parametrize("family,shape,dtype,regime", _range_ids())
+def test_range_case_is_not_vacuous(family, shape, dtype, regime):
+    """Per (family, shape, regime) of the GPU table, for EVERY epilogue combination the GPU test runs:
+
+    w_sub / x_sub: every non-zero weight / activation (second input included) is a non-zero fp16 subnormal, and the expected tensor
+        differs from flushed_reference in at least half of its elements.
+    out_sub: at least 64 non-zero subnormals in the expected tensor; where the combination has a bias, at least 8 exact ties and 8
+        roundings off a tie.  (og_conv1x1_tiled_*'s bias-less combination with one input sums integers times 2^-21: every value is
+        an fp16 subnormal or a small normal exactly, there is nothing to round -- its subnormals are counted, ties cannot exist.)
+        og_conv1x1_heads_* writes fp32: the counts are of what a rounding to fp16 would do to its expected values.
+    overflow: between 1 % and 50 % of the expected tensor is +-inf (heads: beyond 65504 and finite), both signs without ReLU, and
+        the tensor differs from saturated(expected).
+    far: one operand magnitude above 65504 and one non-zero operand below 2^-24."""
+    assert dtype == cx.REGIME_DTYPE[regime]
+    ops, rows = _range_expectations(family, shape, regime)
+    heads = family == 'conv1x1_heads'
+    if regime in ('w_sub', 'x_sub'):
+        for name in (('w', 'w2') if regime == 'w_sub' else ('x', 'x2')):
+            if name in ops:
+                t = ops[name][ops[name] != 0]
+                assert t.numel() > 0 and bool((t.abs() < cx.F16_MIN_NORMAL).all()) and bool((t.half() != 0).all()), name
+    if regime == 'far':
+        mags = torch.cat([ops[k].abs().flatten() for k in ops if k != 'bias'])
+        assert bool((mags > cx.F16_MAX).any()) and bool(((mags > 0) & (mags < 2.0 ** -24)).any())
+    for (b, s, r), v, exp, fl in rows:
+        what = f'bias={b} skip={s} relu={r}'
+        c = cx.range_coverage(v, dtype, None if heads else exp)
+        if regime in ('w_sub', 'x_sub'):
+            assert int((exp != fl).sum()) * 2 >= exp.numel(), what
+        if regime == 'out_sub':
+            assert c['subnormals'] >= 64, (what, c)
+            assert not b or (c['ties'] >= 8 and c['nonties'] >= 8), (what, c)
+        if regime == 'overflow':
+            assert 0.01 * c['elements'] <= c['infs'] <= 0.5 * c['elements'], (what, c['infs'] / c['elements'])
+            big = v.float().half() if heads else exp
+            assert bool((big == float('inf')).any()) and (r or bool((big == -float('inf')).any())), what
+            assert bool(exp.isfinite().all()) if heads else not torch.equal(exp, cx.saturated(exp)), what
+
+
+@pytest.mark.parametrize("family", ['conv3x3', 'conv2d', 'conv2d_proj', 'conv_band', 'conv3x3_tiled', 'conv3x3_tiled_up2',
+                                    'conv3x3s2_tiled', 'conv1x1_tiled', 'stem7x7'])
+def test_out_sub_reaches_the_smallest_normal_from_below(family):
+    """Per 16-bit output family, over its out_sub cases: at least one expected element rounds UP to 2^-14, the smallest normal, from a
+    value below it (a single small case need not hold one; the family does)."""
+    import test_gpu_conv_exact as t
+    n = sum(cx.range_coverage(v, torch.float16, exp)['to_min_normal']
+            for shape in t.RANGE_CASES[family] for _, v, exp, _ in _range_expectations(family, shape, 'out_sub')[1])
+    assert n >= 1, family

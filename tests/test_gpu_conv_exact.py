@@ -8,7 +8,12 @@ A dropped or mis-addressed tap, channel, halo pixel or K slice, a wrong rounding
 CASES is the table the parametrisation is built from: the shapes tests/test_gpu_backbone.py uses for the entry point, edge shapes
 (each asserted supported by the kernel's own query first -- the pointwise kernels, the heads and the stem have no query: their return
 code is the answer), and the shapes the strict fp16 engine launches at four input sizes; test_engine_launches_are_all_in_the_table
-records those launches and keeps the table complete when the routing thresholds of models/engine.py move."""
+records those launches and keeps the table complete when the routing thresholds of models/engine.py move.
+
+RANGE_CASES x RANGE_MODES (test_*_range) run the same bodies with the operands scaled by powers of two to the ends of the 16-bit range
+(conv_exact.REGIMES): fp16 subnormal weights, subnormal activations, outputs in the subnormal range, outputs beyond 65504; bf16 far
+outside fp16's exponents.  Still torch.equal against the one expected tensor; flushed_reference and saturated(expected) appear in a
+failure's message only, to name its kind."""
 import ctypes as C
 import zlib
 
@@ -127,6 +132,32 @@ TILED_UNSPLIT = [(1, 4, 40, 128, 128), (1, 4, 20, 64, 128), (16, 20, 20, 384, 38
 
 _coverage = {}        # (family, dtype) -> [changed, ties, elements, cases]: the rounding really exercised, per case family
 
+# The ends of the 16-bit range (conv_exact.REGIMES): the smallest shapes of CASES that still reach each path -- every one is in
+# CASES, so its *_supported query is known to hold -- times the four fp16 regimes and bf16's 'far'.
+RANGE_CASES = {
+    'conv3x3': [(1, 5, 13, 64, 64), (1, 1, 2, 512, 512), (2, 32, 32, 64, 128)],
+    'conv2d': [(1, 9, 15, 64, 128, 3, 2), (1, 3, 3, 512, 512, 1, 1), (1, 16, 8, 128, 128, 1, 1)],
+    'conv2d_proj': [(1, 2, 3, 64, 128, 3, 5, 128, 2), (1, 5, 13, 128, 64, 5, 13, 64, 1)],
+    'conv_band': [(1, 5, 7, 64, 32, 2, None), (1, 3, 4, 128, 64, 1, (5, 7, 64, 2)), (1, 16, 16, 64, 16, 1, None)],
+    # 16x16, 40x4 and 20x4 tiles, both sides of the K split
+    'conv3x3_tiled': [(1, 16, 32, 64, 128), (1, 16, 16, 512, 512), (1, 4, 40, 192, 128), (1, 4, 40, 128, 128), (1, 4, 20, 128, 128)],
+    'conv3x3_tiled_up2': [(1, 16, 16, 64, 128), (1, 4, 40, 192, 128), (1, 4, 20, 64, 128)],
+    'conv3x3s2_tiled': [(1, 16, 32, 512, 128), (1, 8, 80, 128, 256)],
+    'conv1x1_tiled': [(1, 15, 17, 64, 128, 1, False), (1, 16, 16, 128, 128, 1, True), (1, 33, 21, 128, 128, 2, False),
+                      (1, 8, 8, 512, 512, 1, True)],
+    # fp32 outputs: the expectation is the exact value; out_sub and overflow must come out unrounded and finite
+    'conv1x1_heads': [(1, 15, 17, 192, (17, 38, 17, 2)), (1, 16, 16, 512, (64,))],
+    # (overflow: only the weights and the bias scale, the images are fp32)
+    'stem7x7': [(1, 32, 64), (3, 32, 32)],
+}
+RANGE_MODES = [(torch.float16, 'w_sub'), (torch.float16, 'x_sub'), (torch.float16, 'out_sub'), (torch.float16, 'overflow'),
+               (torch.bfloat16, 'far')]
+# (family, shape) -> a step on s where the formula's share of infinities leaves 1 .. 50 % (test_conv_exact_cpu.py).  At 1x2 pixels
+# only 2 of the 9 taps ever see a pixel: the live K is 1024, not the 4608 the formula is given, and s = 7 left 0 .. 0.1 %; s = 8
+# gives 3.7 .. 7.4 %.
+OVERFLOW_SHIFT = {('conv3x3', (1, 1, 2, 512, 512)): 1}
+_range_coverage = {}  # (family, regime) -> {conv_exact.RANGE_COUNTS, 'cases'}: kept apart from _coverage
+
 
 @pytest.fixture(scope="module")
 def dev():
@@ -139,8 +170,19 @@ def _params(family):
     return [pytest.param(s, id='-'.join(str(v).replace(' ', '') for v in s)) for s in CASES[family]]
 
 
+def _range_params(family):
+    return [pytest.param(s, d, r, id='-'.join(str(v).replace(' ', '') for v in s) + f"-{str(d).split('.')[1]}-{r}")
+            for s in RANGE_CASES[family] for d, r in RANGE_MODES]
+
+
 def _seed(family, shape):
     return zlib.crc32(repr((family, shape)).encode())
+
+
+def _operands(family, shape, regime, *args, **kw):
+    """The operands of one case: those of the default regime (same seed, same draws) scaled into `regime`."""
+    return cx.exact_operands(_seed(family, shape), *args, regime=regime, shift=OVERFLOW_SHIFT.get((family, shape), 0),
+                             x_fp32=family == 'stem7x7', **kw)
 
 
 def _cl(t, dev, dtype):
@@ -151,11 +193,29 @@ def _nan_like(n, c, h, w, dev, dtype):
     return torch.full((n, c, h, w), float('nan'), dtype=dtype, device=dev).contiguous(memory_format=torch.channels_last)
 
 
-def _assert_equal(got, exp, what):
-    assert torch.equal(got, exp), f'{what}: {cx.describe_mismatch(got, exp)}'
+def _assert_equal(got, exp, what, kinds=None):
+    """kinds (the range regimes): () -> {name: alternative expectation}, evaluated on a mismatch only, for the message alone."""
+    if not torch.equal(got, exp):
+        raise AssertionError(f'{what}: {cx.describe_mismatch(got, exp)}' + (cx.describe_kind(got, exp, kinds()) if kinds else ''))
 
 
-def _cover(family, dtype, v64, last, expected=None):
+def _kinds(regime, expected, flushed):
+    """None in the default regime; else what a mismatch is counted against: flushed() and saturated(expected) (fp32 outputs cannot
+    saturate: the value rounded to the 16-bit type instead)."""
+    if regime is None:
+        return None
+    if expected.dtype == torch.float32:
+        return lambda: {'flushed_reference': flushed(), 'the value rounded to 16 bits': expected.to(cx.REGIME_DTYPE[regime]).float()}
+    return lambda: {'flushed_reference': flushed(), 'saturated(expected)': cx.saturated(expected)}
+
+
+def _cover(family, dtype, v64, last, expected=None, regime=None):
+    if regime is not None:
+        c = _range_coverage.setdefault((family, regime), dict.fromkeys(cx.RANGE_COUNTS + ('cases',), 0))
+        for k, v in cx.range_coverage(v64, dtype, expected).items():
+            c[k] += v
+        c['cases'] += int(last)
+        return
     changed, ties, total = cx.rounding_coverage(v64, dtype, expected)
     c = _coverage.setdefault((family, dtype), [0, 0, 0, 0])
     c[0] += changed
@@ -169,37 +229,39 @@ def _zeros_ws(need, dev):
     return torch.zeros(need, dtype=torch.uint8, device=dev)
 
 
-def _run_twice(launch, make_out, expected, what):
+def _run_twice(launch, make_out, expected, what, kinds=None):
     """Two launches, each into a fresh NaN-filled (or freshly cloned) output; both must equal the expectation: tickets and slabs are
     back at rest after the first."""
     for i in range(2):
         out = make_out()
         launch(out)
-        _assert_equal(out, expected, f'{what}, launch {i + 1}')
+        _assert_equal(out, expected, f'{what}, launch {i + 1}', kinds)
 
 
-def _splitk_case(dev, family, dtype, ops, dims, ws, call, second=None, combos=SKIP_RELU):
+def _splitk_case(dev, family, dtype, ops, dims, ws, call, second=None, combos=SKIP_RELU, regime=None):
     """Shared body of the split-K families: dims = (n, ho, wo, cout, stride); call(x, w, bias, skip, out, relu) launches."""
     n, ho, wo, cout, stride = dims
     x, bias = _cl(ops['x'], dev, dtype), ops['bias'].to(dev)
     res = _cl(ops['res'], dev, dtype)
     x2 = _cl(ops['x2'], dev, dtype) if second else None
-    base = cx.exact_sum(x, ops['w'].to(dev), stride=stride, x2=x2, w2=ops['w2'].to(dev) if second else None,
-                        stride2=second if second else 1)
+    wd, w2 = ops['w'].to(dev), ops['w2'].to(dev) if second else None
+    st2 = second if second else 1
+    base = cx.exact_sum(x, wd, stride=stride, x2=x2, w2=w2, stride2=st2)
     for ci, (use_skip, relu) in enumerate(combos):
-        v64 = cx.apply_epilogue(base, bias, res if use_skip else None, relu)
-        _cover(family, dtype, v64, ci == len(combos) - 1)
-        _run_twice(lambda out: call(x, x2, bias, res if use_skip else None, out, relu),
-                   lambda: _nan_like(n, cout, ho, wo, dev, dtype), cx.round_once(v64, dtype), f'skip={use_skip} relu={relu}')
+        skip = res if use_skip else None
+        v64 = cx.apply_epilogue(base, bias, skip, relu)
+        _cover(family, dtype, v64, ci == len(combos) - 1, regime=regime)
+        exp = cx.round_once(v64, dtype)
+        _run_twice(lambda out: call(x, x2, bias, skip, out, relu), lambda: _nan_like(n, cout, ho, wo, dev, dtype), exp,
+                   f'skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, wd, bias, skip, relu, stride, x2, w2, st2, dtype)))
     assert ws[:256].count_nonzero().item() == 0                    # the zero page is never written
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv3x3'))
-def test_conv3x3_exact(dev, shape, dtype):
+def _conv3x3_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout = shape
     lib = _lib.load()
-    ops = cx.exact_operands(_seed('conv3x3', shape), n, h, w, cin, cout)
+    ops = _operands('conv3x3', shape, regime, n, h, w, cin, cout)
     wt = _cl(ops['w'], dev, dtype)
     ws = _zeros_ws(lib.og_conv3x3_workspace_bytes(n * h * w, cin, cout), dev)
     fn = _lib.lp(lib, 'og_conv3x3', dtype)
@@ -207,15 +269,24 @@ def test_conv3x3_exact(dev, shape, dtype):
     def call(x, x2, bias, skip, out, relu):
         _lib.check(fn(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(skip) if skip is not None else None, _lib.ptr(out), n, h, w,
                       cin, cout, relu, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
-    _splitk_case(dev, 'conv3x3', dtype, ops, (n, h, w, cout, 1), ws, call)
+    _splitk_case(dev, 'conv3x3', dtype, ops, (n, h, w, cout, 1), ws, call, regime=regime)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv2d'))
-def test_conv2d_exact(dev, shape, dtype):
+@pytest.mark.parametrize("shape", _params('conv3x3'))
+def test_conv3x3_exact(dev, shape, dtype):
+    _conv3x3_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv3x3'))
+def test_conv3x3_range(dev, shape, dtype, regime):
+    _conv3x3_case(dev, shape, dtype, regime)
+
+
+def _conv2d_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout, k, st = shape
     lib = _lib.load()
-    ops = cx.exact_operands(_seed('conv2d', shape), n, h, w, cin, cout, k, st)
+    ops = _operands('conv2d', shape, regime, n, h, w, cin, cout, k, st)
     ho, wo = ops['res'].shape[2:]
     wt = _cl(ops['w'], dev, dtype)
     ws = _zeros_ws(lib.og_conv2d_workspace_bytes(n, h, w, cin, cout, k, st), dev)
@@ -224,16 +295,24 @@ def test_conv2d_exact(dev, shape, dtype):
     def call(x, x2, bias, skip, out, relu):
         _lib.check(fn(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(skip) if skip is not None else None, _lib.ptr(out), n, h, w,
                       cin, cout, k, st, relu, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
-    _splitk_case(dev, 'conv2d', dtype, ops, (n, ho, wo, cout, st), ws, call)
+    _splitk_case(dev, 'conv2d', dtype, ops, (n, ho, wo, cout, st), ws, call, regime=regime)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv2d_proj'))
-def test_conv2d_proj_exact(dev, shape, dtype):
-    """act(conv3x3(y) + conv1x1(x, stride2) + bias): the projection's weights appended along K, as _Residual.w_cat builds them."""
+@pytest.mark.parametrize("shape", _params('conv2d'))
+def test_conv2d_exact(dev, shape, dtype):
+    _conv2d_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv2d'))
+def test_conv2d_range(dev, shape, dtype, regime):
+    _conv2d_case(dev, shape, dtype, regime)
+
+
+def _conv2d_proj_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout, h2, w2, cin2, st2 = shape
     lib = _lib.load()
-    ops = cx.exact_operands(_seed('conv2d_proj', shape), n, h, w, cin, cout, second=(h2, w2, cin2))
+    ops = _operands('conv2d_proj', shape, regime, n, h, w, cin, cout, second=(h2, w2, cin2))
     w_cat = torch.cat([ops['w'].permute(0, 2, 3, 1).reshape(cout, -1), ops['w2'].reshape(cout, -1)], 1).to(dev).to(dtype).contiguous()
     ws = _zeros_ws(lib.og_conv2d_proj_workspace_bytes(n, h, w, cin, cout, 3, 1, cin2), dev)
     fn = _lib.lp(lib, 'og_conv2d_proj', dtype)
@@ -242,17 +321,28 @@ def test_conv2d_proj_exact(dev, shape, dtype):
         assert skip is None
         _lib.check(fn(_lib.ptr(x), _lib.ptr(w_cat), _lib.ptr(bias), _lib.ptr(x2), _lib.ptr(out), n, h, w, cin, cout, 3, 1, h2, w2, cin2,
                       st2, relu, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), lib)
-    _splitk_case(dev, 'conv2d_proj', dtype, ops, (n, h, w, cout, 1), ws, call, second=st2, combos=((False, 1), (False, 0)))
+    _splitk_case(dev, 'conv2d_proj', dtype, ops, (n, h, w, cout, 1), ws, call, second=st2, combos=((False, 1), (False, 0)),
+                 regime=regime)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv_band'))
-def test_conv_band_exact(dev, shape, dtype):
+@pytest.mark.parametrize("shape", _params('conv2d_proj'))
+def test_conv2d_proj_exact(dev, shape, dtype):
+    """act(conv3x3(y) + conv1x1(x, stride2) + bias): the projection's weights appended along K, as _Residual.w_cat builds them."""
+    _conv2d_proj_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv2d_proj'))
+def test_conv2d_proj_range(dev, shape, dtype, regime):
+    _conv2d_proj_case(dev, shape, dtype, regime)
+
+
+def _conv_band_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout, st, proj = shape
     lib = _lib.load()
     h2, w2, c2, st2 = proj if proj is not None else (0, 0, 0, 1)
     assert lib.og_conv_band_supported(n, h, w, cin, cout, st, h2, w2, c2, st2) > 0
-    ops = cx.exact_operands(_seed('conv_band', shape), n, h, w, cin, cout, 3, st, second=(h2, w2, c2) if proj else None)
+    ops = _operands('conv_band', shape, regime, n, h, w, cin, cout, 3, st, second=(h2, w2, c2) if proj else None)
     ho, wo = ops['res'].shape[2:]
     x, bias, res = _cl(ops['x'], dev, dtype), ops['bias'].to(dev), _cl(ops['res'], dev, dtype)
     wt = _cl(ops['w'], dev, dtype)
@@ -262,21 +352,36 @@ def test_conv_band_exact(dev, shape, dtype):
     _lib.check(lib.og_conv_band_pack_w16(_lib.ptr(wt), _lib.ptr(wp) if proj else None, cin, cout, c2, _lib.ptr(packed),
                                          _lib.stream_ptr(dev)), lib)
     fn = _lib.lp(lib, 'og_conv_band', dtype)
-    base = cx.exact_sum(x, ops['w'].to(dev), stride=st, x2=x2, w2=ops['w2'].to(dev) if proj else None, stride2=st2)
+    wd, w2d = ops['w'].to(dev), ops['w2'].to(dev) if proj else None
+    base = cx.exact_sum(x, wd, stride=st, x2=x2, w2=w2d, stride2=st2)
     for ci, (use_skip, relu) in enumerate(SKIP_RELU):
-        v64 = cx.apply_epilogue(base, bias, res if use_skip else None, relu)
-        _cover('conv_band', dtype, v64, ci == len(SKIP_RELU) - 1)
+        skip = res if use_skip else None
+        v64 = cx.apply_epilogue(base, bias, skip, relu)
+        _cover('conv_band', dtype, v64, ci == len(SKIP_RELU) - 1, regime=regime)
+        exp = cx.round_once(v64, dtype)
 
         def launch(out):
             _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(res) if use_skip else None,
                           _lib.ptr(x2) if proj else None, _lib.ptr(out), n, h, w, cin, cout, st, relu, h2, w2, c2, st2,
                           _lib.stream_ptr(dev)), lib)
-        _run_twice(launch, lambda: _nan_like(n, cout, ho, wo, dev, dtype), cx.round_once(v64, dtype), f'skip={use_skip} relu={relu}')
+        _run_twice(launch, lambda: _nan_like(n, cout, ho, wo, dev, dtype), exp, f'skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, wd, bias, skip, relu, st, x2, w2d, st2, dtype)))
 
 
-def _tiled_setup(lib, dev, dtype, family, shape, order, stride, up=False):
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", _params('conv_band'))
+def test_conv_band_exact(dev, shape, dtype):
+    _conv_band_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv_band'))
+def test_conv_band_range(dev, shape, dtype, regime):
+    _conv_band_case(dev, shape, dtype, regime)
+
+
+def _tiled_setup(lib, dev, dtype, family, shape, order, stride, up=False, regime=None):
     n, h, w, cin, cout = shape
-    ops = cx.exact_operands(_seed(family, shape), n, h, w, cin, cout, 3, stride, up=up)
+    ops = _operands(family, shape, regime, n, h, w, cin, cout, 3, stride, up=up)
     wt = _cl(ops['w'], dev, dtype)
     packed = torch.empty(wt.numel(), dtype=dtype, device=dev)
     _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(wt), cin, cout, order, _lib.ptr(packed), _lib.stream_ptr(dev)), lib)
@@ -284,24 +389,64 @@ def _tiled_setup(lib, dev, dtype, family, shape, order, stride, up=False):
     return ops, packed, x, bias, res, cx.exact_sum(x, ops['w'].to(dev), stride=stride)
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv3x3_tiled'))
-def test_conv3x3_tiled_exact(dev, shape, dtype):
+def _conv3x3_tiled_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout = shape
     lib = _lib.load()
     assert lib.og_conv3x3_tiled_supported(n, h, w, cin, cout) > 0
-    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3_tiled', shape, 0, 1)
+    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3_tiled', shape, 0, 1, regime=regime)
     need = lib.og_conv3x3_tiled_workspace_bytes(n, h, w, cin, cout)
     ws = torch.zeros(need, dtype=torch.uint8, device=dev) if need else None
     fn = _lib.lp(lib, 'og_conv3x3_tiled', dtype)
     for ci, (use_skip, relu) in enumerate(SKIP_RELU):
-        v64 = cx.apply_epilogue(base, bias, res if use_skip else None, relu)
-        _cover('conv3x3_tiled', dtype, v64, ci == len(SKIP_RELU) - 1)
+        skip = res if use_skip else None
+        v64 = cx.apply_epilogue(base, bias, skip, relu)
+        _cover('conv3x3_tiled', dtype, v64, ci == len(SKIP_RELU) - 1, regime=regime)
+        exp = cx.round_once(v64, dtype)
 
         def launch(out):
             _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(res) if use_skip else None, _lib.ptr(out), n, h, w,
                           cin, cout, relu, _lib.ptr(ws) if need else None, need, _lib.stream_ptr(dev)), lib)
-        _run_twice(launch, lambda: _nan_like(n, cout, h, w, dev, dtype), cx.round_once(v64, dtype), f'skip={use_skip} relu={relu}')
+        _run_twice(launch, lambda: _nan_like(n, cout, h, w, dev, dtype), exp, f'skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, ops['w'].to(dev), bias, skip, relu, dtype=dtype)))
+    if need:
+        assert ws[:256].count_nonzero().item() == 0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", _params('conv3x3_tiled'))
+def test_conv3x3_tiled_exact(dev, shape, dtype):
+    _conv3x3_tiled_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv3x3_tiled'))
+def test_conv3x3_tiled_range(dev, shape, dtype, regime):
+    _conv3x3_tiled_case(dev, shape, dtype, regime)
+
+
+def _conv3x3_tiled_up2_case(dev, shape, dtype, regime=None):
+    n, h, w, cin, cout = shape
+    lib = _lib.load()
+    assert lib.og_conv3x3_tiled_supported(n, h, w, cin, cout) > 0
+    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3_tiled_up2', shape, 0, 1, up=True, regime=regime)
+    up = _cl(ops['up'], dev, dtype)
+    need = lib.og_conv3x3_tiled_workspace_bytes(n, h, w, cin, cout)
+    ws = torch.zeros(need, dtype=torch.uint8, device=dev) if need else None
+    fn = _lib.lp(lib, 'og_conv3x3_tiled_up2', dtype)
+    for ci, (use_skip, relu) in enumerate(SKIP_RELU):
+        skip = res if use_skip else None
+        raw = cx.apply_epilogue(base, bias, skip, relu)
+        low = cx.round_once(raw, dtype)                                                                      # first rounding
+        v64 = up.double() + low.double().repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+        exp = cx.round_once(v64, dtype)                                                                      # second rounding
+        # coverage: the expectation against the never-rounded up + nearest2x(raw) -- either rounding point may have moved it
+        _cover('conv3x3_tiled_up2', dtype, up.double() + raw.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3),
+               ci == len(SKIP_RELU) - 1, expected=exp, regime=regime)
+
+        def launch(out):
+            _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(res) if use_skip else None, _lib.ptr(out), n, h, w,
+                          cin, cout, relu, _lib.ptr(ws) if need else None, need, _lib.stream_ptr(dev)), lib)
+        _run_twice(launch, lambda: up.clone(memory_format=torch.preserve_format), exp, f'skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, ops['w'].to(dev), bias, skip, relu, dtype=dtype, up=up)))
     if need:
         assert ws[:256].count_nonzero().item() == 0
 
@@ -311,57 +456,48 @@ def test_conv3x3_tiled_exact(dev, shape, dtype):
 def test_conv3x3_tiled_up2_exact(dev, shape, dtype):
     """up += nearest_x2(round(act(conv + bias + skip))), rounded again: the kernel's contract has two rounding points
     (include/og_decoder.h: og_conv3x3_tiled_up2_bf16; models/hourglass_104.py:170-176) and the expectation restates them one by one."""
+    _conv3x3_tiled_up2_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv3x3_tiled_up2'))
+def test_conv3x3_tiled_up2_range(dev, shape, dtype, regime):
+    _conv3x3_tiled_up2_case(dev, shape, dtype, regime)
+
+
+def _conv3x3s2_tiled_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout = shape
     lib = _lib.load()
-    assert lib.og_conv3x3_tiled_supported(n, h, w, cin, cout) > 0
-    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3_tiled_up2', shape, 0, 1, up=True)
-    up = _cl(ops['up'], dev, dtype)
-    need = lib.og_conv3x3_tiled_workspace_bytes(n, h, w, cin, cout)
-    ws = torch.zeros(need, dtype=torch.uint8, device=dev) if need else None
-    fn = _lib.lp(lib, 'og_conv3x3_tiled_up2', dtype)
+    assert lib.og_conv3x3s2_tiled_supported(n, h, w, cin, cout) > 0
+    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3s2_tiled', shape, 1, 2, regime=regime)
+    fn = _lib.lp(lib, 'og_conv3x3s2_tiled', dtype)
     for ci, (use_skip, relu) in enumerate(SKIP_RELU):
-        raw = cx.apply_epilogue(base, bias, res if use_skip else None, relu)
-        low = cx.round_once(raw, dtype)                                                                      # first rounding
-        v64 = up.double() + low.double().repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
-        # coverage: the expectation against the never-rounded up + nearest2x(raw) -- either rounding point may have moved it
-        _cover('conv3x3_tiled_up2', dtype, up.double() + raw.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3),
-               ci == len(SKIP_RELU) - 1, expected=cx.round_once(v64, dtype))
+        skip = res if use_skip else None
+        v64 = cx.apply_epilogue(base, bias, skip, relu)
+        _cover('conv3x3s2_tiled', dtype, v64, ci == len(SKIP_RELU) - 1, regime=regime)
+        exp = cx.round_once(v64, dtype)
 
         def launch(out):
             _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(res) if use_skip else None, _lib.ptr(out), n, h, w,
-                          cin, cout, relu, _lib.ptr(ws) if need else None, need, _lib.stream_ptr(dev)), lib)
-        _run_twice(launch, lambda: up.clone(memory_format=torch.preserve_format), cx.round_once(v64, dtype),        # second rounding
-                   f'skip={use_skip} relu={relu}')
-    if need:
-        assert ws[:256].count_nonzero().item() == 0
+                          cin, cout, relu, _lib.stream_ptr(dev)), lib)
+        _run_twice(launch, lambda: _nan_like(n, cout, h // 2, w // 2, dev, dtype), exp, f'skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, ops['w'].to(dev), bias, skip, relu, 2, dtype=dtype)))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", _params('conv3x3s2_tiled'))
 def test_conv3x3s2_tiled_exact(dev, shape, dtype):
-    n, h, w, cin, cout = shape
-    lib = _lib.load()
-    assert lib.og_conv3x3s2_tiled_supported(n, h, w, cin, cout) > 0
-    ops, packed, x, bias, res, base = _tiled_setup(lib, dev, dtype, 'conv3x3s2_tiled', shape, 1, 2)
-    fn = _lib.lp(lib, 'og_conv3x3s2_tiled', dtype)
-    for ci, (use_skip, relu) in enumerate(SKIP_RELU):
-        v64 = cx.apply_epilogue(base, bias, res if use_skip else None, relu)
-        _cover('conv3x3s2_tiled', dtype, v64, ci == len(SKIP_RELU) - 1)
-
-        def launch(out):
-            _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(res) if use_skip else None, _lib.ptr(out), n, h, w,
-                          cin, cout, relu, _lib.stream_ptr(dev)), lib)
-        _run_twice(launch, lambda: _nan_like(n, cout, h // 2, w // 2, dev, dtype), cx.round_once(v64, dtype),
-                   f'skip={use_skip} relu={relu}')
+    _conv3x3s2_tiled_case(dev, shape, dtype)
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv1x1_tiled'))
-def test_conv1x1_tiled_exact(dev, shape, dtype):
-    """One input (stride 1 / 2) and two inputs concatenated along K, with and without bias (null: the raw projection)."""
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv3x3s2_tiled'))
+def test_conv3x3s2_tiled_range(dev, shape, dtype, regime):
+    _conv3x3s2_tiled_case(dev, shape, dtype, regime)
+
+
+def _conv1x1_tiled_case(dev, shape, dtype, regime=None):
     n, h, w, cin, cout, st, two = shape
     lib = _lib.load()
-    ops = cx.exact_operands(_seed('conv1x1_tiled', shape), n, h, w, cin, cout, 1, st, second=(h, w, cin) if two else None)
+    ops = _operands('conv1x1_tiled', shape, regime, n, h, w, cin, cout, 1, st, second=(h, w, cin) if two else None)
     ho, wo = ops['res'].shape[2:]
     x1, bias, res = _cl(ops['x'], dev, dtype), ops['bias'].to(dev), _cl(ops['res'], dev, dtype)
     x2 = _cl(ops['x2'], dev, dtype) if two else None
@@ -370,28 +506,40 @@ def test_conv1x1_tiled_exact(dev, shape, dtype):
     packed = torch.empty(wcat.numel(), dtype=dtype, device=dev)
     _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(wcat), wcat.shape[1], cout, 2, _lib.ptr(packed), _lib.stream_ptr(dev)), lib)
     fn = _lib.lp(lib, 'og_conv1x1_tiled', dtype)
-    base = cx.exact_sum(x1, ops['w'].to(dev), stride=st, x2=x2, w2=ops['w2'].to(dev) if two else None, stride2=st)
+    wd, w2d = ops['w'].to(dev), ops['w2'].to(dev) if two else None
+    base = cx.exact_sum(x1, wd, stride=st, x2=x2, w2=w2d, stride2=st)
     for ci, (use_bias, use_skip, relu) in enumerate(BIAS_SKIP_RELU):
-        v64 = cx.apply_epilogue(base, bias if use_bias else None, res if use_skip else None, relu)
-        _cover('conv1x1_tiled', dtype, v64, ci == len(BIAS_SKIP_RELU) - 1)
+        b, skip = bias if use_bias else None, res if use_skip else None
+        v64 = cx.apply_epilogue(base, b, skip, relu)
+        _cover('conv1x1_tiled', dtype, v64, ci == len(BIAS_SKIP_RELU) - 1, regime=regime)
+        exp = cx.round_once(v64, dtype)
 
         def launch(out):
             _lib.check(fn(_lib.ptr(x1), cin, h, w, st, _lib.ptr(x2) if two else None, cin if two else 0, h, w, st, _lib.ptr(packed),
                           _lib.ptr(bias) if use_bias else None, _lib.ptr(res) if use_skip else None, _lib.ptr(out), n, ho, wo, cout,
                           relu, _lib.stream_ptr(dev)), lib)
-        _run_twice(launch, lambda: _nan_like(n, cout, ho, wo, dev, dtype), cx.round_once(v64, dtype),
-                   f'bias={use_bias} skip={use_skip} relu={relu}')
+        _run_twice(launch, lambda: _nan_like(n, cout, ho, wo, dev, dtype), exp, f'bias={use_bias} skip={use_skip} relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x1, wd, b, skip, relu, st, x2, w2d, st, dtype)))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('conv1x1_heads'))
-def test_conv1x1_heads_exact(dev, shape, dtype):
-    """fp32 NCHW outputs written from the fp32 accumulators, bias added in fp32: the expectation is the exact value itself."""
+@pytest.mark.parametrize("shape", _params('conv1x1_tiled'))
+def test_conv1x1_tiled_exact(dev, shape, dtype):
+    """One input (stride 1 / 2) and two inputs concatenated along K, with and without bias (null: the raw projection)."""
+    _conv1x1_tiled_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv1x1_tiled'))
+def test_conv1x1_tiled_range(dev, shape, dtype, regime):
+    _conv1x1_tiled_case(dev, shape, dtype, regime)
+
+
+def _conv1x1_heads_case(dev, shape, dtype, regime=None):
     n, h, w, cin, heads = shape
     lib = _lib.load()
     tot = sum(heads)
     cout = (tot + 63) // 64 * 64
-    ops = cx.exact_operands(_seed('conv1x1_heads', shape), n, h, w, cin, tot, 1)
+    ops = _operands('conv1x1_heads', shape, regime, n, h, w, cin, tot, 1)
     x = _cl(ops['x'], dev, dtype)
     wt = torch.zeros(cout, cin, dtype=dtype, device=dev)
     wt[:tot] = ops['w'].reshape(tot, cin).to(dev).to(dtype)
@@ -400,6 +548,10 @@ def test_conv1x1_heads_exact(dev, shape, dtype):
     packed = torch.empty(wt.numel(), dtype=dtype, device=dev)
     _lib.check(lib.og_conv3x3_pack_w16(_lib.ptr(wt), cin, cout, 3, _lib.ptr(packed), _lib.stream_ptr(dev)), lib)
     exp = cx.exact_reference(x, ops['w'].to(dev), ops['bias'].to(dev), dtype=torch.float32)
+    assert bool(exp.isfinite().all())
+    if regime is not None:
+        _cover('conv1x1_heads', dtype, exp.double(), True, regime=regime)      # (what a rounding to 16 bits WOULD do to the values)
+    kinds = _kinds(regime, exp, lambda: cx.flushed_reference(x, ops['w'].to(dev), ops['bias'].to(dev), dtype=torch.float32))
     chans = (C.c_int * len(heads))(*heads)
     for i in range(2):
         outs = [torch.full((n, c, h, w), float('nan'), device=dev) for c in heads]
@@ -408,17 +560,28 @@ def test_conv1x1_heads_exact(dev, shape, dtype):
                                                          chans, ptrs, _lib.stream_ptr(dev)), lib)
         c0 = 0
         for hi, (o, c) in enumerate(zip(outs, heads)):
-            _assert_equal(o, exp[:, c0:c0 + c], f'head {hi}, launch {i + 1}')
+            _assert_equal(o, exp[:, c0:c0 + c], f'head {hi}, launch {i + 1}',
+                          kinds and (lambda: {k: v[:, c0:c0 + c] for k, v in kinds().items()}))
             c0 += c
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", _params('stem7x7'))
-def test_stem7x7_exact(dev, shape, dtype):
-    """fp32 NCHW integer images in (their conversion to 16 bits is exact), weights packed [cout][ky][8 taps][4 channels] as the engine does."""
+@pytest.mark.parametrize("shape", _params('conv1x1_heads'))
+def test_conv1x1_heads_exact(dev, shape, dtype):
+    """fp32 NCHW outputs written from the fp32 accumulators, bias added in fp32: the expectation is the exact value itself."""
+    _conv1x1_heads_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('conv1x1_heads'))
+def test_conv1x1_heads_range(dev, shape, dtype, regime):
+    """The exact value in fp32 again: below 2^-14 (out_sub) and beyond 65504 (overflow) it comes out unrounded and finite."""
+    _conv1x1_heads_case(dev, shape, dtype, regime)
+
+
+def _stem7x7_case(dev, shape, dtype, regime=None):
     n, h, w = shape
     lib = _lib.load()
-    ops = cx.exact_operands(_seed('stem7x7', shape), n, h, w, 3, 128, 7, 2)
+    ops = _operands('stem7x7', shape, regime, n, h, w, 3, 128, 7, 2)
     x, bias = ops['x'].to(dev).contiguous(), ops['bias'].to(dev)
     packed = torch.zeros((128, 7, 8, 4), device=dev)
     packed[:, :, :7, :3] = ops['w'].to(dev).permute(0, 2, 3, 1)
@@ -428,10 +591,26 @@ def test_stem7x7_exact(dev, shape, dtype):
     assert tuple(base.shape) == (n, 128, h // 2, w // 2)
     for relu in (1, 0):
         v64 = cx.apply_epilogue(base, bias, None, relu)
-        _cover('stem7x7', dtype, v64, relu == 0)
+        _cover('stem7x7', dtype, v64, relu == 0, regime=regime)
+        exp = cx.round_once(v64, dtype)
         _run_twice(lambda out: _lib.check(fn(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), n, h, w, relu,
                                              _lib.stream_ptr(dev)), lib),
-                   lambda: _nan_like(n, 128, h // 2, w // 2, dev, dtype), cx.round_once(v64, dtype), f'relu={relu}')
+                   lambda: _nan_like(n, 128, h // 2, w // 2, dev, dtype), exp, f'relu={relu}',
+                   _kinds(regime, exp, lambda: cx.flushed_reference(x, ops['w'].to(dev), bias, None, relu, 2, dtype=dtype)))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", _params('stem7x7'))
+def test_stem7x7_exact(dev, shape, dtype):
+    """fp32 NCHW integer images in (their conversion to 16 bits is exact), weights packed [cout][ky][8 taps][4 channels] as the engine does."""
+    _stem7x7_case(dev, shape, dtype)
+
+
+@pytest.mark.parametrize("shape,dtype,regime", _range_params('stem7x7'))
+def test_stem7x7_range(dev, shape, dtype, regime):
+    """The fp32 images are of the regime's size (x_sub: the kernel's own conversion must produce the subnormals); under overflow only
+    the weights and the bias are scaled."""
+    _stem7x7_case(dev, shape, dtype, regime)
 
 
 def test_tiled_edge_shapes_sit_on_both_sides_of_the_k_split():
@@ -453,6 +632,32 @@ def test_rounding_is_exercised_in_every_family():
             judged += 1
             assert changed >= 0.25 * total and ties >= 1, (family, dtype, changed / total, ties)
     assert judged == 0 or judged == 2 * (len(CASES) - 1), f'{judged} (family, dtype) pairs judged'
+
+
+@pytest.mark.parametrize("dtype,regime", RANGE_MODES)
+def test_device_casts_keep_the_regime_operands(dev, dtype, regime):
+    """What _cl does to a regime's operands on the device -- fp32 -> 16 bits, channels-last -- is what the CPU cast does: subnormals
+    and all.  (A cast that flushed them would make a correct kernel look like flushed_reference.)"""
+    ops = cx.exact_operands(1, 1, 5, 7, 64, 32, second=(5, 7, 64), up=True, regime=regime)
+    for name, t in ops.items():
+        if name != 'bias':
+            src = t if t.dim() == 4 else t[:, :, None, None]
+            assert torch.equal(_cl(src, dev, dtype).cpu(), src.to(dtype)) and torch.equal(src.to(dtype).float(), src), name
+
+
+def test_range_regimes_are_exercised_in_every_family():
+    """Per case family and regime, over the expected tensors of the range cases above (all epilogue combinations): the elements
+    compared, the subnormals, exact ties and infinities among them -- printed; a family whose cases have all run must show the
+    regime's point (og_conv1x1_heads_* writes fp32: its counts are of what a rounding to 16 bits would do to its expected values).
+    Kept apart from _coverage: the 25 % condition above is about the default regime alone."""
+    judged = 0
+    for (family, regime), c in sorted(_range_coverage.items()):
+        print(f"{family} {regime}: {c['elements']} elements compared, {c['subnormals']} subnormals, {c['ties']} ties, {c['infs']} infs, "
+              f"{c['nonties']} other roundings, {c['to_min_normal']} rounded up to the smallest normal, {c['cases']} cases")
+        if c['cases'] == len(RANGE_CASES[family]):
+            judged += 1
+            assert c['elements'] > 0 and (regime != 'out_sub' or c['subnormals'] >= 64 * c['cases']) and (regime != 'overflow' or c['infs'] > 0)
+    assert judged in (0, len(RANGE_CASES) * len(RANGE_MODES)), f'{judged} (family, regime) pairs judged'
 
 
 # ---------------------------------------------------------------------------------------- the engine's launches are in the table
