@@ -862,6 +862,44 @@ int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows
 int og_fold_row_words(void);
 int og_fold_bn_w16(const int64_t *rows, const int32_t *wg_prefix, int n_rows, int n_workgroups, int f16, void *stream);
 
+/* ---- range report: what the engine's 16-bit type does to a tensor, counted on the device (models/range_report.py,
+ * InferenceEngine.weight_report / probe=True; csrc/range.hip) ----  A stats row is OG_RANGE_WORDS = 9 int64 words that every call
+ * ACCUMULATES into; a row of zeros is the identity (a fresh row is zeros).  For an element x of source type S (OG_RANGE_F32 /
+ * OG_RANGE_F16 / OG_RANGE_BF16) and the target type T (OG_RANGE_F16 / OG_RANGE_BF16; S is fp32 or T): y = x rounded to T, to nearest
+ * even, subnormals kept -- the cast of og_fold_bn_w16 -- and y = x when S = T.  Every class is decided on BIT PATTERNS with integer
+ * comparisons (abs = the pattern without its sign; a 16-bit source is widened to fp32 exactly), so no denormal mode changes a count:
+ *     [0] n      elements seen
+ *     [1] nan    x is a NaN (any payload)
+ *     [2] inf    x is +-inf
+ *     [3] over   x finite, y = +-inf       fp16: |x| >= 65520 (abs >= 0x477ff000);  bf16: abs >= 0x7f7f8000;  0 when S = T
+ *     [4] zero   x = +-0
+ *     [5] flush  x != 0, y = +-0           fp16: |x| <= 2^-25 (abs <= 0x33000000);  bf16: abs <= 0x00008000;  0 when S = T
+ *     [6] sub    y is a non-zero subnormal of T    fp16: 2^-25 < |x| < 1023.5 * 2^-24 (the tie rounds to the normal 2^-14)
+ *     [7] max    max over finite x of the fp32 bit pattern of |x|
+ *     [8] min    max over finite non-zero x of 0x7f800000 - (fp32 bit pattern of |x|): 0 = none seen, else the smallest non-zero
+ *                magnitude is the fp32 whose pattern is 0x7f800000 - [8]
+ * Words 0..6 are sums and words 7, 8 maxima: the result does not depend on any order, is exact and the same on every run.
+ * og_range_stats: a table in device memory, `rows` int64[n_rows][4] = [pointer, numel, source type, stats row index], and
+ * `wg_prefix` int32[n_rows + 1], the running sum of the rows' workgroup counts from 0 to n_workgroups; a row's workgroups share its
+ * chunks of og_range_chunk_elems() elements in turn (a row needs at most ceil(numel / chunk) of them, a row of no elements none).
+ * Several table rows may name one stats row; `stats` int64[.][9] holds every row the table names.  One launch.
+ * og_range_probe: one tensor whose pointer and size are kernel arguments (inside a graph capture a tensor's address is not the one
+ * of the warm-up passes: a device table would have to be rewritten), into the one row `stats_row`.
+ * Both: tensors are dense runs of numel elements, aligned to their element size, any offset beyond that (16-byte loads between a
+ * scalar head and tail; nothing outside the run is read); numel = 0 touches nothing; no allocation, no workspace, no
+ * synchronisation, graph-capturable.  OG_EINVAL (nothing launched): a null or misaligned table, stats or tensor; n_rows <= 0; a
+ * negative count; a target that is not a 16-bit type; og_range_probe: a source that is neither fp32 nor the target.  The table's
+ * contents are device memory and are not validated: its builder answers for addresses, counts and stats row indices; a table row
+ * whose source type the launch does not serve is passed over. */
+#define OG_RANGE_WORDS 9
+#define OG_RANGE_F32 0
+#define OG_RANGE_F16 1
+#define OG_RANGE_BF16 2
+int og_range_chunk_elems(void);
+int og_range_stats(const int64_t *rows, const int32_t *wg_prefix, int n_rows, int n_workgroups, int target, int64_t *stats,
+                   void *stream);
+int og_range_probe(const void *x, int64_t numel, int source, int target, int64_t *stats_row, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

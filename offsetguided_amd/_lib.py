@@ -132,6 +132,9 @@ SIGNATURES = {
     "og_sgd_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp]),
     "og_fold_row_words": (_i, []),
     "og_fold_bn_w16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "og_range_chunk_elems": (_i, []),
+    "og_range_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "og_range_probe": (_i, [_vp, C.c_int64, _i, _i, _vp, _vp]),
 }
 
 # fp16 twins of the 16-bit-type specific entry points (csrc/lp_dtype.h): same signatures

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libog_decoder.so")
-SOURCES = ["abi.cpp", "nms_topk.hip", "upsample.hip", "collect.hip", "group.hip", "flip.hip", "epilogue.hip", "losses.hip", "conv3x3.hip", "conv_band.hip", "encoder.hip", "stem.hip", "preprocess.hip", "scale_merge.hip", "scored_offset.hip", "nms_window.hip", "draw.hip", "views.hip", "augment.hip", "jpeg_sim.hip", "oks.hip", "coco_mask.hip", "optim.hip", "fold.hip"]
+SOURCES = ["abi.cpp", "nms_topk.hip", "upsample.hip", "collect.hip", "group.hip", "flip.hip", "epilogue.hip", "losses.hip", "conv3x3.hip", "conv_band.hip", "encoder.hip", "stem.hip", "preprocess.hip", "scale_merge.hip", "scored_offset.hip", "nms_window.hip", "draw.hip", "views.hip", "augment.hip", "jpeg_sim.hip", "oks.hip", "coco_mask.hip", "optim.hip", "fold.hip", "range.hip"]
 # the 16-bit-type specific files are compiled a second time for fp16 (csrc/lp_dtype.h)
 F16_SOURCES = ["conv3x3.hip", "conv_band.hip", "epilogue.hip", "stem.hip"]
 ARCH = "gfx950"

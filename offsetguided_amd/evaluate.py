@@ -71,6 +71,11 @@ def evaluate_cli(argv=None):
                         help="paint every batch's poses over the network-input images on the device (visualization.draw_poses) and "
                              'write the first image of each batch to <show-dir>/<dump-name>.poses.<batch>.ppm')
     parser.add_argument('--show-dir', default='.', type=str, help='directory of the --show-* images')
+    parser.add_argument('--range-report', default=None, type=str, metavar='FILE',
+                        help="count on the device what the engine's 16-bit type does to every layer -- folded weights that overflow, "
+                             'flush to zero or go subnormal; activations that are inf, NaN or subnormal over the images actually run '
+                             '(engines built with probe=True: a diagnostic mode that reads every activation a second time) -- and '
+                             'write the report as JSON to FILE')
     parser.add_argument('--show-hmp-idx', default=None, type=int, metavar='N',
                         help='paint heat-map channel N of the decoded maps over the first image of each batch, raw and after NMS '
                              '(visualization.draw_heatmap): <show-dir>/<dump-name>.hmpN.<batch>.ppm and .hmpN_nms.<batch>.ppm')
@@ -233,6 +238,9 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     no wait in it), `engines_built`, `torch_conv_calls` (0: every engine is strict, models/engine.py), `test_scales` and
     `engines_per_shape` (input shape 'NxCxHxW' -> engines kept for it), with args.show_detected_poses `pose_images` and with
     args.show_hmp_idx / show_limb_idx / show_all_limbs `view_images` (the files written).
+    args.range_report (--range-report FILE): the engines are built with probe=True, and at the end their probe rows, summed by probe
+    name over engines, shapes and lanes, go with the first engine's weight_report() to FILE as JSON and to stats['range']
+    (range_summary below).  Without it no call is added.
     args.test_scales (--test-scales, default [1.0]): more than one scale runs the multi-scale test (enqueue_multi_scale below)."""
     if not torch.cuda.is_available():
         raise RuntimeError('run_images needs a HIP device (offsetguided_amd has no CPU path)')
@@ -259,6 +267,8 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
     batch_time, end, last_print, pending = AverageMeter(), time.time(), -1, collections.deque()
     full_batch = None
     first_engine = [None]
+    range_file = getattr(args, 'range_report', None)
+    range_parts, range_images = [], [0]           # [(probe points, probe rows on the host)] of the engines that have gone; images forwarded
 
     # --show-detected-poses (evaluate.py:267-284): a batch's handle also carries (batch index, uint8 copy of the network-input batch);
     # once its poses are on the host they are painted over that copy on the device, in network-input coordinates (before
@@ -357,13 +367,16 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
             if len(engines) >= ENGINE_CACHE:
                 while pending:               # the batches in flight still read the outputs of the engines that go
                     collect(pending.popleft())
-                engines.popitem(last=False)
+                for gone in engines.popitem(last=False)[1]:
+                    if range_file:
+                        range_parts.append((gone[0]._probe_points, gone[0].probe_stats.cpu()))
             of_shape = []
         engines[shape] = of_shape          # most recently used last
         slot = min(of_shape, key=lambda e: e[1], default=None)           # the engine of this shape that has rested longest
         if slot is None or (batch_idx - slot[1] < len(lanes) and len(of_shape) < len(lanes)):
             slot = [models.InferenceEngine(model, shape[0], shape[2], shape[3], device=dev,
-                                           feat_stage=args.feat_stage, like=first_engine[0]), -len(lanes), None]
+                                           feat_stage=args.feat_stage, like=first_engine[0], **({'probe': True} if range_file else {})),
+                    -len(lanes), None]
             first_engine[0] = first_engine[0] or slot[0]      # the module's weights do not change inside one call
             of_shape.append(slot)
             if stats is not None:
@@ -435,6 +448,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                 # scale by scale: forward, then its merge, then the engine's event -- two scales of one padded size may share an engine,
                 # whose graph outputs the second forward overwrites (stream order: after the first merge has read them)
                 hm, off, *rest = slot[0].forward_raw(x)
+                range_images[0] += x.shape[0]
                 scl = rest.pop(0) if has_scl else None
                 jit = rest.pop(0) if has_jit else None
                 mode = multiscale.MODE_WRITE if s == 0 else (multiscale.MODE_ADD_SCALE if s == len(inputs) - 1 else multiscale.MODE_ADD)
@@ -479,6 +493,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     lanes[lane].wait_event(slot[2])              # the engine's last batch (maybe on another lane): its decoder has read the outputs
                 with torch.cuda.stream(lanes[lane]):
                     outputs = slot[0](images)
+                    range_images[0] += images.shape[0]
                     handle = (processors[lane].submit(outputs, flip_test=args.flip_test, cat_flip_offs=args.cat_flip_offset,
                                                       scored_off=scored_off), metas) + shown
                     if views:      # before the engine's event: the views read its outputs
@@ -503,6 +518,15 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
                     args.batch_size / (batch_time.avg or per_batch)))
         while pending:
             collect(pending.popleft())
+        if range_file:
+            torch.cuda.synchronize(dev)
+            range_parts += [(e[0]._probe_points, e[0].probe_stats.cpu()) for of in engines.values() for e in of]
+            report = range_summary(first_engine[0], range_parts, range_images[0])
+            with open(range_file, 'w') as f:
+                json.dump(report, f, indent=1)
+            print(report['summary']['verdict'])
+            if stats is not None:
+                stats['range'] = report
     finally:
         # also on an exception (engine build failure, OgError, the --fixed-height assertion): the worker must not outlive the
         # call holding pinned staging buffers, and a pack still queued must not write one while the caller handles the error
@@ -513,6 +537,44 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
             stats['test_scales'] = list(scales)
             stats['engines_per_shape'] = {'x'.join(str(v) for v in shape): len(of) for shape, of in engines.items()}
     return result_keypoints, result_image_ids
+
+
+def range_summary(engine, parts, images):
+    """The --range-report dict: {dtype, images, weights, activations, summary}.  parts: [(probe points, (points, 9) int64 rows)] of
+    every engine that ran; rows of one probe name are combined over engines, shapes and lanes (counts summed, max / min combined) and
+    listed in the first engine's issue order.  images: the images forwarded (the flipped copies of --flip-test and the padding of a
+    ragged last batch included: every probe's n is images x its elements per image).  weights: engine.weight_report()."""
+    from .models import range_report
+    merged, order = {}, []
+    for points, rows in parts:
+        for (name, route, shape, riders), row in zip(points, rows):
+            if name not in merged:
+                order.append(name)
+                merged[name] = {'name': name, 'route': route, 'with': list(riders), 'shapes': [], 'rows': []}
+            entry = merged[name]
+            if list(shape) not in entry['shapes']:
+                entry['shapes'].append(list(shape))
+            entry['rows'].append(row.reshape(1, -1))
+    activations = []
+    for name in order:
+        entry = merged[name]
+        words = range_report.decode(range_report.combine(entry.pop('rows')))[0]
+        activations.append({**entry, **{k: words[k] for k in ('n', 'nan', 'inf', 'sub', 'zero', 'max', 'min')}})
+    weights = engine.weight_report()
+    bad = next((a for a in activations if a['inf'] + a['nan'] > 0), None)
+    top = max(activations, key=lambda a: a['max'], default=None)
+    over = [w['name'] for w in weights if w['folded']['over'] > 0]
+    flush = [w['name'] for w in weights if w['folded']['flush'] > 0]
+    dtype = str(engine.dtype).replace('torch.', '')
+    summary = {'first_nonfinite_activation': {k: bad[k] for k in ('name', 'route', 'inf', 'nan')} if bad else None,
+               'weights_over': over, 'weights_flush': flush,
+               'max_activation': {'name': top['name'], 'value': top['max']} if top else None}
+    summary['verdict'] = (f'range report ({dtype}, {images} images): '
+                          + (f"first non-finite activation at {bad['name']} ({bad['inf']} inf, {bad['nan']} NaN)" if bad else
+                             'no non-finite activation')
+                          + f'; {len(over)} layers with overflowing and {len(flush)} with flushed folded weights'
+                          + (f"; largest activation {top['max']:.6g} at {top['name']}" if top else ''))
+    return {'dtype': dtype, 'images': images, 'weights': weights, 'activations': activations, 'summary': summary}
 
 
 class DeviceFeeder:

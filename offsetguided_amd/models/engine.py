@@ -78,9 +78,9 @@ def _cl(t):
     return t if t is None or _is_cl(t) else t.contiguous(memory_format=torch.channels_last)
 
 
-def _epilogue(y, bias32, bias_lp, skip, relu, fused):
+def _epilogue(y, bias32, bias_lp, skip, relu, fused, name=None):
     """y = act(y + bias (+ skip)) in place.  fused: one hand-written HIP pass (og_bias_act_bf16);
-    otherwise plain torch ops (CPU / fp32 checking path)."""
+    otherwise plain torch ops (CPU / fp32 checking path).  name: the layer, for a probing engine."""
     if fused:
         n, c, h, w = y.shape
         assert _is_cl(y) and (skip is None or skip.shape == y.shape)
@@ -88,6 +88,7 @@ def _epilogue(y, bias32, bias_lp, skip, relu, fused):
         lib = _lib.load()
         _lib.check(_lib.lp(lib, 'og_bias_act', y.dtype)(_lib.ptr(y), _lib.ptr(bias32), _lib.ptr(skip) if skip is not None else None,
                                         n * h * w, c, int(relu), _lib.stream_ptr(y.device)), lib)
+        _probe(name or 'bias_act', 'bias_act', y)
         return y
     y += bias_lp.view(1, -1, 1, 1)
     if skip is not None:
@@ -173,6 +174,29 @@ def _torch_conv(name, x, weight, stride=1, padding=0):
     return F.conv2d(x, weight, None, stride, padding)
 
 
+def _probe(name, route, t, riders=(), source=None):
+    """A probe point: `t` is the activation the launch just queued on the current stream produced, `name` the layer, `route` its
+    launcher, `riders` the layers that rode along in that launch.  Nothing unless the issuing engine was built with probe=True: then
+    one og_range_probe launch behind it on the same stream (stream-ordered, so right inside the forked branches too) into the row
+    of this point, numbered by issue order; the first pass of an engine only lists the points (InferenceEngine._size_probes)."""
+    eng = _issuer.eng
+    if eng is None or not eng.probe:
+        return
+    from . import range_report
+    i = eng._probe_i
+    eng._probe_i += 1
+    entry = (name, route, tuple(t.shape), tuple(riders))
+    if eng.probe_stats is None:
+        eng._probe_points.append(entry)
+        return
+    if i >= len(eng._probe_points) or eng._probe_points[i] != entry:
+        raise _lib.OgError(f'probe {i}: this pass issues {entry}, the first pass issued '
+                           f'{eng._probe_points[i] if i < len(eng._probe_points) else "fewer launches"}')
+    range_report.probe(t, eng.dtype, eng.probe_stats, i)
+    if eng.probe_tap is not None and not torch.cuda.is_current_stream_capturing():
+        eng.probe_tap(name, t)
+
+
 _warm_streams = {}
 _n_engines = 0
 _side_owner = {}        # handle of a side stream -> the (device, engine) it was made for
@@ -226,7 +250,9 @@ class _Conv:
         fake = self._whatif_skipped(x)
         if fake is not None:
             return fake
-        return _torch_conv(self.name, x, self.w, self.stride, self.pad)
+        y = _torch_conv(self.name, x, self.w, self.stride, self.pad)
+        _probe(self.name + ':raw', 'torch', y)
+        return y
 
     def _whatif_skipped(self, x):
         """OG_ENGINE_WHATIF=<classes> (diagnostic, WRONG RESULTS): layers of the named classes produce an uninitialised
@@ -309,7 +335,7 @@ class _Conv:
             return fake
         how = self.route(tuple(x.shape), x.dtype, x.is_cuda, _is_cl(x))
         if how == 'torch':
-            return _epilogue(self.raw(x), self.b32, self.b, skip, self.relu, self.fused)
+            return _epilogue(self.raw(x), self.b32, self.b, skip, self.relu, self.fused, self.name)
         return {'band': self.band, 'tiled': self._tiled, 'splitk': self._splitk, 'tiled_s2': self._tiled_s2}[how](x, skip)
 
     def _packed(self, order, other=None):
@@ -363,10 +389,11 @@ class _Conv:
         t = nxt.w_band if nxt.w_band is not None else (nxt.w_tiled if nxt.w_tiled is not None else (nxt.w_alt if nxt.w_alt is not None else nxt.w))
         lib.og_conv_next_weights_hint(_lib.ptr(t), t.numel() * t.element_size())
 
-    def _launch(self, lib, fn, ins, out, ints, need=None):
+    def _launch(self, lib, fn, ins, out, ints, need=None, route=None, riders=()):
         """What every launcher ends with, its packing and layout copies done: allocate `out` (a shape; a tensor is updated in place),
         fetch the workspace (need: its bytes; None: the kernel takes none), warm the next layer's weights, then
-        fn(*ins, out, *ints[, workspace, bytes], stream) with the tensors of `ins` (None: a null pointer) as pointers.  -> out"""
+        fn(*ins, out, *ints[, workspace, bytes], stream) with the tensors of `ins` (None: a null pointer) as pointers.  -> out
+        route, riders: the launcher's name and the layers that ride along, for a probing engine (_probe: `out` as it is after the launch)."""
         x = ins[0]
         if not isinstance(out, torch.Tensor):
             out = torch.empty(tuple(out), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
@@ -374,6 +401,7 @@ class _Conv:
         ws = () if need is None else (_lib.ptr(buf), buf.numel()) if need else (None, 0)
         self.warm_next(lib)
         _lib.check(fn(*[_lib.ptr(t) if t is not None else None for t in ins], _lib.ptr(out), *ints, *ws, _lib.stream_ptr(x.device)), lib)
+        _probe(self.name, route, out, riders)
         return out
 
     def band(self, x, skip=None, x2=None, proj=None):
@@ -385,7 +413,8 @@ class _Conv:
         x, skip, x2 = _cl(x), _cl(skip), _cl(x2) if proj is not None else None
         _, c2, h2, w2 = x2.shape if proj is not None else (0, 0, 0, 0)
         return self._launch(lib, _lib.lp(lib, 'og_conv_band', x.dtype), (x, self.w_band, self.b32, skip, x2), self.out_shape(x.shape),
-                            (n, h, w, c, self.w.shape[0], self.stride[0], int(self.relu), h2, w2, c2, proj.stride[0] if proj is not None else 1))
+                            (n, h, w, c, self.w.shape[0], self.stride[0], int(self.relu), h2, w2, c2, proj.stride[0] if proj is not None else 1),
+                            route='band+proj' if proj is not None else 'band', riders=(proj.name,) if proj is not None else ())
 
     def _tiled(self, x, skip):
         """3x3 stride 1 on og_conv3x3_tiled_*; the 40- and 20-wide levels split K: tickets + fp32 slabs in the workspace."""
@@ -395,7 +424,7 @@ class _Conv:
         wt = self._packed(0)
         x, skip = _cl(x), _cl(skip)
         return self._launch(lib, _lib.lp(lib, 'og_conv3x3_tiled', x.dtype), (x, wt, self.b32, skip), self.out_shape(x.shape),
-                            (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout))
+                            (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout), route='tiled')
 
     def up2(self, x, skip, up):
         """up += nearest_x2(act(conv(x) + bias + skip)) in one launch (up: (N, Cout, 2H, 2W) channels-last, in place): the merge of
@@ -408,7 +437,7 @@ class _Conv:
         wt = self._packed(0)
         x, skip = _cl(x), _cl(skip)
         self._launch(lib, _lib.lp(lib, 'og_conv3x3_tiled_up2', x.dtype), (x, wt, self.b32, skip), up,
-                     (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout))
+                     (n, h, w, c, cout, int(self.relu)), lib.og_conv3x3_tiled_workspace_bytes(n, h, w, c, cout), route='up2')
 
     def _tiled_s2(self, x, skip):
         """3x3 stride 2 on og_conv3x3s2_tiled_* (the large down-sampling layers: 320 -> 160, 160 -> 80), epilogue fused; x is
@@ -417,7 +446,7 @@ class _Conv:
         lib = _lib.load()
         wt = self._packed(1)
         return self._launch(lib, _lib.lp(lib, 'og_conv3x3s2_tiled', x.dtype), (x, wt, self.b32, _cl(skip)), self.out_shape(x.shape),
-                            (n, h, w, c, self.w.shape[0], int(self.relu)))
+                            (n, h, w, c, self.w.shape[0], int(self.relu)), route='tiled_s2')
 
     def _splitk(self, x, skip):
         """3x3 stride 1 | 2 on the split-K kernel og_conv2d_* (raw channels-last weights, fp32 slabs in the workspace)."""
@@ -426,7 +455,7 @@ class _Conv:
         lib = _lib.load()
         x, skip = _cl(x), _cl(skip)
         return self._launch(lib, _lib.lp(lib, 'og_conv2d', x.dtype), (x, self.w, self.b32, skip), self.out_shape(x.shape),
-                            (n, h, w, c, cout, 3, st, int(self.relu)), lib.og_conv2d_workspace_bytes(n, h, w, c, cout, 3, st))
+                            (n, h, w, c, cout, 3, st, int(self.relu)), lib.og_conv2d_workspace_bytes(n, h, w, c, cout, 3, st), route='splitk')
 
     def pointwise(self, x, x2=None, other=None, bias=True, skip=None):
         """act(W x (+ W_other x2) + bias (+ skip)) in one launch on og_conv1x1_tiled_*; `other` = the second 1x1 layer of the junction
@@ -445,6 +474,7 @@ class _Conv:
             _lib.ptr(x), c, h, w, st, _lib.ptr(x2) if x2 is not None else None, c if x2 is not None else 0, h, w, st,
             _lib.ptr(wt), _lib.ptr(self.b32) if bias else None, _lib.ptr(skip) if skip is not None else None, _lib.ptr(out),
             n, ho, wo, cout, int(self.relu and bias), _lib.stream_ptr(x.device)), lib)
+        _probe(self.name, 'pointwise', out, (other.name,) if other is not None else ())
         return out
 
 
@@ -503,7 +533,7 @@ class _Residual:
         lib = _lib.load()
         return self.c2._launch(lib, _lib.lp(lib, 'og_conv2d_proj', y.dtype), (y, self.w_cat, self.c2.b32, x), (n, cout, h, w),
                                (n, h, w, c, cout, 3, 1, h2, w2, c2, self.skip.stride[0], 1),
-                               lib.og_conv2d_proj_workspace_bytes(n, h, w, c, cout, 3, 1, c2))
+                               lib.og_conv2d_proj_workspace_bytes(n, h, w, c, cout, 3, 1, c2), route='splitk+proj', riders=(self.skip.name,))
 
 
 def _heads_tiled_ok(cin, heads, channels_last=True):
@@ -621,6 +651,7 @@ class _Level:
             n, c, h, w = up.shape
             lib = _lib.load()
             _lib.check(_lib.lp(lib, 'og_upsample2_add', up.dtype)(_lib.ptr(up), _lib.ptr(low), n, h, w, c, _lib.stream_ptr(up.device)), lib)
+            _probe(self.low3[-1].c2.name + ':merge', 'upsample2_add', up)
         else:
             up += F.interpolate(low, scale_factor=2, mode='nearest')
         return up
@@ -716,21 +747,26 @@ class _Layers:
             if h is not None:
                 yield h, None
 
+    def _pairs(self, model, convs, what='refresh'):
+        """[(torch conv, BatchNorm or None)] of `model` for the (_Conv, partner) list `convs`, found again by name."""
+        mods = dict(model.named_modules())
+        pairs = []
+        for c, _ in convs:
+            if c.name not in mods or (c.bn_name is not None and c.bn_name not in mods):
+                raise ValueError(f'{what}: the module has no layer {c.name!r}: not the architecture this engine was built from')
+            conv, bn = mods[c.name], mods[c.bn_name] if c.bn_name is not None else None
+            if tuple(conv.weight.shape) != tuple(c.w.shape) or (bn is not None and not isinstance(bn, _BatchNorm)):
+                raise ValueError(f'{what}: layer {c.name!r} is {tuple(conv.weight.shape)} in the module, {tuple(c.w.shape)} in the engine')
+            pairs.append((conv, bn))
+        return pairs
+
     def refresh(self, model, events=None):
         """Fold `model`'s current weights into the bundle's EXISTING tensors: w, b32, b of every _Conv (one og_fold_bn_w16 launch on a
         fused bundle, torch's _fold copied in place otherwise), then every derived image that exists.  No tensor changes address.  The
         caller (InferenceEngine.refresh) brackets this with device synchronisation.  events: a list that receives the (start, end)
         HIP timing events round the fold launch (tools/engine_refresh_bench.py)."""
-        mods = dict(model.named_modules())
         convs = list(self._convs())
-        pairs = []
-        for c, _ in convs:
-            if c.name not in mods or (c.bn_name is not None and c.bn_name not in mods):
-                raise ValueError(f'refresh: the module has no layer {c.name!r}: not the architecture this engine was built from')
-            conv, bn = mods[c.name], mods[c.bn_name] if c.bn_name is not None else None
-            if tuple(conv.weight.shape) != tuple(c.w.shape) or (bn is not None and not isinstance(bn, _BatchNorm)):
-                raise ValueError(f'refresh: layer {c.name!r} is {tuple(conv.weight.shape)} in the module, {tuple(c.w.shape)} in the engine')
-            pairs.append((conv, bn))
+        pairs = self._pairs(model, convs)
         with torch.no_grad():
             if self.fused:
                 from . import fold
@@ -856,7 +892,7 @@ class InferenceEngine:
     rounding error) or torch.float32 (plain torch ops: the checking path)."""
 
     def __init__(self, model, batch, height, width, dtype=torch.float16, device='cuda:0', feat_stage=-1,
-                 use_graph=True, like=None, strict=None):
+                 use_graph=True, like=None, strict=None, probe=False):
         assert height % 128 == 0 and width % 128 == 0, 'Hourglass-104 needs multiples of max_stride=128'
         global _n_engines
         self._id = _n_engines            # scratch (split-K slabs, tickets) is per engine: two engines may be in flight
@@ -875,6 +911,15 @@ class InferenceEngine:
         # torch_conv_calls lists every such layer met since the engine was made (warm-up passes, capture and eager forwards)
         self.strict = (self.fused and os.environ.get('OG_ENGINE_STRICT', '1') != '0') if strict is None else bool(strict)
         self.torch_conv_calls = []
+        # probe=True (a diagnostic mode: every activation is read a second time): one og_range_probe launch behind every launch that
+        # produces an activation, into one row each of probe_stats (int64 (points, 9), include/og_decoder.h "range report"), captured
+        # into the graph so that every replay accumulates: activation_report() / reset_probes().  probe_tap: a callable (name, tensor)
+        # an eager engine hands every probed tensor to.  probe=False: probe_stats is None and no launch is added.
+        self.probe = bool(probe)
+        if self.probe and not self.fused:
+            raise _lib.OgError(f'InferenceEngine(probe=True) needs a 16-bit engine on a GPU; this one is {dtype} on {self.device}')
+        self.probe_stats, self.probe_tap = None, None
+        self._probe_points, self._probe_i = [], 0
         # folded / tiled / packed weights do not depend on the input shape: engines of one (model state, dtype, device, stage)
         # share them (evaluate.run_images builds one engine per input shape, --fixed-height: one per width)
         # like = an engine the caller built for this very module a moment ago (evaluate.run_images: one per shape and lane): its
@@ -893,9 +938,14 @@ class InferenceEngine:
         self._out = None
         if use_graph:
             self._capture()
+        elif self.probe:
+            with torch.no_grad():
+                self._forward(self._static_in)          # lists the probe points
+            self._size_probes()
 
     def _forward(self, images):
         _issuer.engine, _issuer.ws, _issuer.eng = self._id, self._ws, self
+        self._probe_i = 0
         try:
             return self._forward_impl(images)
         finally:
@@ -909,6 +959,7 @@ class InferenceEngine:
             x = torch.empty((n, 128, h // 2, w // 2), dtype=self.dtype, device=images.device, memory_format=torch.channels_last)
             _lib.check(_lib.lp(lib, 'og_stem7x7', self.dtype)(_lib.ptr(images), _lib.ptr(self.stem_w), _lib.ptr(self.pre[0].b32), _lib.ptr(x),
                                            n, h, w, 1, _lib.stream_ptr(images.device)), lib)
+            _probe(self.pre[0].name, 'stem', x)
             inter = self.pre[1](x)
         else:
             if self.fused:   # fp32 NCHW -> bf16 NHWC in one pass
@@ -917,6 +968,7 @@ class InferenceEngine:
                 n, c, h, w = images.shape
                 x = torch.empty((n, c, h, w), dtype=self.dtype, device=images.device, memory_format=torch.channels_last)
                 _lib.check(_lib.lp(lib, 'og_nchw_f32_to_nhwc', self.dtype)(_lib.ptr(images), _lib.ptr(x), n, c, h, w, _lib.stream_ptr(images.device)), lib)
+                _probe('input', 'nchw_to_nhwc', x)
             else:
                 x = images.to(self.dtype).contiguous(memory_format=torch.channels_last)
             inter = _run(self.pre, x)
@@ -948,16 +1000,19 @@ class InferenceEngine:
             ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
             _lib.check(_lib.lp(lib, 'og_conv1x1_heads', feat.dtype)(_lib.ptr(feat), c, _lib.ptr(packed), _lib.ptr(bpad), n, h, w, cout,
                                                                 len(outs), chans, ptrs, _lib.stream_ptr(feat.device)), lib)
+            for head, o in zip(self._heads(), outs):      # fp32 maps: what the engine's type would make of them
+                _probe(head.name, 'heads', o)
             return tuple(outs)
         if self.heads_w is not None:
             lib = _lib.load()
             y = _torch_conv('heads', feat, self.heads_w)
             n, cc, h, w = y.shape
             outs, c0 = [], 0
-            for ch in self.head_channels:
+            for head, ch in zip(self._heads(), self.head_channels):
                 o = torch.empty((n, ch, h, w), dtype=torch.float32, device=y.device)
                 _lib.check((lib.og_nhwc_f16_to_nchw_f32 if y.dtype == torch.float16 else lib.og_nhwc_bf16_to_nchw_f32)(_lib.ptr(y), cc, c0, ch, _lib.ptr(self.heads_b), _lib.ptr(o), n, h, w,
                                                         _lib.stream_ptr(y.device)), lib)
+                _probe(head.name, 'heads_glue', o)
                 outs.append(o)
                 c0 += ch
             return tuple(outs)
@@ -973,8 +1028,12 @@ class InferenceEngine:
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):                      # warm-up: weight tiling / packing, workspaces, allocator
                 self._forward(self._static_in)
+                if self.probe and self.probe_stats is None:
+                    self._size_probes()             # the first pass listed the probe points; the second one warms the probes up
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
+        if self.probe:
+            self.probe_stats.zero_()                # the warm-up's counts go; the captured probes accumulate from zero
         # the warm-up stream goes back with the side streams of the 32nd engine before this one (every engine MAKES eight streams: that
         # keeps each engine's branches on the hardware queues the first engine's sit on -- _lib.new_stream)
         _warm_streams[(self.device.index, self._id)] = side
@@ -983,6 +1042,72 @@ class InferenceEngine:
         self._graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self._graph):
             self._out = self._forward(self._static_in)
+
+    def _heads(self):
+        return [h for h in (self.hm, self.off, self.scale, self.jitter) if h is not None]
+
+    # ---- range report (include/og_decoder.h "range report", models/range_report.py) ---------------------------------------------
+    def _size_probes(self):
+        """The rows of the probe points the first pass listed: one persistent tensor, zeros."""
+        assert self._probe_points, 'probe=True, but the forward has no probe point'
+        self.probe_stats = torch.zeros((len(self._probe_points), 9), dtype=torch.int64, device=self.device)
+
+    def reset_probes(self):
+        """Clear the probe rows (queued on the current stream, no wait)."""
+        if self.probe_stats is None:
+            raise _lib.OgError('reset_probes: the engine was built with probe=False')
+        self.probe_stats.zero_()
+        return self
+
+    def activation_report(self):
+        """What the probes counted since the engine was built or reset_probes(): one dict per probe point, in issue order --
+        name (the layer), route (its launcher), shape, with (the layers that rode along in that launch) and n, nan, inf, sub, zero,
+        max, min of the header's nine words (max, min: magnitudes, 0.0 = none seen).  Waits for the device."""
+        if self.probe_stats is None:
+            raise _lib.OgError('activation_report: the engine was built with probe=False')
+        from . import range_report
+        torch.cuda.synchronize(self.device)
+        rows = range_report.decode(self.probe_stats)
+        return [{'name': name, 'route': route, 'shape': list(shape), 'with': list(riders),
+                 **{k: r[k] for k in ('n', 'nan', 'inf', 'sub', 'zero', 'max', 'min')}}
+                for (name, route, shape, riders), r in zip(self._probe_points, rows)]
+
+    def weight_report(self, model=None):
+        """Per convolution of the bundle (the walk and the names of refresh()), two stats rows of the header's nine words:
+        `stored`, the 16-bit weights the kernels read (source = target = the engine's type), and `folded`, the fp32 result of folding
+        `model`'s layer (default: the module refresh() would use) BEFORE the cast -- its over / flush / sub say how many weights
+        the engine's type turns into inf, into 0 and into subnormals.  ONE og_range_stats launch for all layers.  -> a list of
+        {name, kind, shape, stored: {...}, folded: {...}}.  Waits for the device."""
+        if not self.fused:
+            raise _lib.OgError(f'weight_report needs a 16-bit engine on a GPU; this one is {self.dtype} on {self.device}')
+        from . import range_report
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+            model = model.module
+        if model is None:
+            model = self._layers.module()
+            if model is None:
+                raise ValueError('weight_report: the module this engine was built from no longer exists; pass one')
+        convs = list(self._layers._convs())
+        pairs = self._layers._pairs(model, convs, 'weight_report')
+        heads = {id(h) for h in self._heads()}
+        tensors, rows, out = [], [], []
+        _issuer.build_device = self.device
+        try:
+            with torch.no_grad(), torch.cuda.device(self.device):
+                for i, ((c, _), (conv, bn)) in enumerate(zip(convs, pairs)):
+                    w = _fold(conv, bn)[0]
+                    tensors += [c.w, w if w.is_contiguous() or _is_cl(w) else w.contiguous()]
+                    rows += [2 * i, 2 * i + 1]
+                    k, st = c.w.shape[2], c.stride[0]
+                    out.append({'name': c.name, 'kind': 'head' if id(c) in heads else f'conv{k}x{k}' + (f's{st}' if st != 1 else ''),
+                                'shape': list(c.w.shape)})
+                stats = range_report.range_stats(tensors, self.dtype, rows)
+        finally:
+            _issuer.build_device = None
+        decoded = range_report.decode(stats)
+        for i, entry in enumerate(out):
+            entry['stored'], entry['folded'] = decoded[2 * i], decoded[2 * i + 1]
+        return out
 
     def refresh(self, model=None):
         """Bring the engine -- and every engine that shares its weight bundle: the other input shapes, both lanes -- to the CURRENT
