@@ -9,7 +9,7 @@
 // streamed straight through registers, no LDS image and one barrier (the channels' scales); otherwise it is the same code with one
 // tap.  The arithmetic is the header's list of individually rounded fp32 operations (-ffp-contract=off, correctly rounded divide and
 // sqrt): tests/engine_refresh_common.py restates it in numpy and the GPU test compares bit for bit.
-#include "og_common.h"
+#include "table.h"
 
 namespace {
 
@@ -17,13 +17,6 @@ constexpr int FOLD_THREADS = 256;
 constexpr int FOLD_LDS_FLOATS = 8192;        // 32 KB: the [tap][channel] image of one pass
 constexpr int FOLD_PAD = 8;                  // floats added to the image's row pitch
 constexpr int FOLD_ROW_WORDS = 16;
-
-typedef __attribute__((address_space(1))) float gfloat;
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) f4 gf4;
-typedef __attribute__((address_space(1))) unsigned short gu16;
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u4 gu4;
 
 struct Layer {
     const gfloat *w, *bias, *gamma, *beta, *mean, *var;
@@ -56,18 +49,6 @@ __device__ __forceinline__ Layer load_layer(const int64_t *rows, int r)
     l.partner = (int)e[14];
     l.slab = (int)e[15];
     return l;
-}
-
-// Row of workgroup `wg`: the largest r < n_rows with prefix[r] <= wg (prefix[n_rows] is the total).
-__device__ __forceinline__ int find_row(const int32_t *prefix, int n_rows, int wg)
-{
-    int lo = 0, hi = n_rows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // fp32 -> the 16-bit type, round to nearest even.  fp16: the hardware conversion (overflow -> inf, subnormals kept); bf16: on the
@@ -105,26 +86,22 @@ template <int T>
 __device__ __forceinline__ void load_pass(const gfloat *src, int n, int taps, int pitch, bool has_scale, float scale, float *tile)
 {
     const int K = T ? T : taps;
-    const int head_max = (int)(((16u - (unsigned)((uintptr_t)src & 15u)) & 15u) >> 2);
-    const int head = head_max < n ? head_max : n;
-    const int n_vec = (n - head) >> 2;
-    const int tail = head + 4 * n_vec;
+    const OgFrame f = og_frame(src, n, 4);
     auto put = [&](int s, float v) {
         if (has_scale) v = v * scale;
         const int ch = s / K, tap = s - ch * K;
         tile[tap * pitch + ch] = v;
     };
-    for (int k = threadIdx.x; k < n_vec; k += FOLD_THREADS) {
-        const int s = head + 4 * k;
+    for (int k = threadIdx.x; k < f.n_vec; k += FOLD_THREADS) {
+        const int s = f.head + 4 * k;
         const f4 v = *(const gf4 *)(src + s);
         put(s, v.x);
         put(s + 1, v.y);
         put(s + 2, v.z);
         put(s + 3, v.w);
     }
-    const int t = threadIdx.x;      // the scalar edges: the head on threads 0.., the tail on threads 64.. (another wave)
-    if (t < head) put(t, src[t]);
-    if (t >= 64 && t - 64 < n - tail) put(tail + t - 64, src[tail + t - 64]);
+    const int e = og_frame_edge(f, n);
+    if (e >= 0) put(e, src[e]);
 }
 
 // tile -> the runs dst[tap * cin + i0 + (0 .. ic)], tap by tap: eight values per 16-byte store where `vec`, else one by one
@@ -156,7 +133,7 @@ template <bool F16>
 __global__ __launch_bounds__(FOLD_THREADS) void fold_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix, int n_rows)
 {
     __shared__ __attribute__((aligned(16))) float tile[FOLD_LDS_FLOATS];
-    const int r = find_row(prefix, n_rows, blockIdx.x);
+    const int r = og_find_row(prefix, n_rows, blockIdx.x);
     const Layer l = load_layer(rows, r);
     if (l.slab <= 0 || l.cout <= 0 || l.cin <= 0 || l.taps <= 0) return;
     const long first = (long)(blockIdx.x - prefix[r]) * l.slab;
@@ -250,9 +227,7 @@ OG_API int og_fold_row_words(void) { return FOLD_ROW_WORDS; }
 OG_API int og_fold_bn_w16(const int64_t *rows, const int32_t *wg_prefix, int n_rows, int n_workgroups, int f16, void *stream)
 {
     const char *name = "og_fold_bn_w16";
-    OG_REQUIRE(rows && wg_prefix, OG_EINVAL, "%s: null table", name);
-    OG_REQUIRE(((uintptr_t)rows & 7u) == 0 && ((uintptr_t)wg_prefix & 3u) == 0, OG_EINVAL, "%s: misaligned table", name);
-    OG_REQUIRE(n_rows > 0 && n_workgroups >= 0, OG_EINVAL, "%s: bad table size (%d rows, %d workgroups)", name, n_rows, n_workgroups);
+    if (int rc = og_check_table(name, rows, wg_prefix, n_rows, n_workgroups)) return rc;
     if (n_workgroups == 0) return OG_OK;
     if (f16)
         hipLaunchKernelGGL(fold_kernel<true>, dim3(n_workgroups), dim3(FOLD_THREADS), 0, (hipStream_t)stream, rows, wg_prefix, n_rows);

@@ -5,7 +5,7 @@
 // header's list of individually rounded fp32 operations (the library is built with -ffp-contract=off, correctly rounded divide and
 // sqrt): tests/optim_common.py restates it in numpy and the GPU tests compare bit for bit.  No float atomics anywhere: the sum of
 // squares goes through per-chunk partials in double and a fixed-order reduction.
-#include "og_common.h"
+#include "table.h"
 
 namespace {
 
@@ -13,12 +13,6 @@ constexpr int OPTIM_THREADS = 256;
 constexpr int OPTIM_CHUNK = 8192;            // elements of one tensor per workgroup: 8 float4 per thread
 constexpr int OPTIM_STATE_BYTES = 16;        // [scale f32, norm f32, dropped i32, pad]; the double partials follow
 constexpr int SCALE_THREADS = 1024;
-
-// The table holds addresses as integers: the pointers made from them are given the global address space, so the loads and stores
-// are global_* instructions and not flat_* ones (a generic pointer would be checked against the LDS and scratch apertures).
-typedef __attribute__((address_space(1))) float gfloat;
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) f4 gf4;
 
 struct Row {
     gfloat *p;
@@ -28,27 +22,15 @@ struct Row {
     long n;
 };
 
-struct Span {          // what a workgroup owns: elements [lo, hi) of its row, vectors of four from vs, n_vec of them, then the tail
-    long lo, hi, vs, tail;
-    int n_vec;
+struct Span {          // what a workgroup owns: elements [lo, hi) of its row; vectors of four from element vs, f.n_vec of them
+    long lo, hi, vs;
+    OgFrame f;
 };
-
-// Row of chunk `chunk`: the largest r < n_rows with prefix[r] <= chunk (prefix[n_rows] is the total).
-__device__ __forceinline__ int find_row(const int32_t *prefix, int n_rows, int chunk)
-{
-    int lo = 0, hi = n_rows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= chunk) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // false: nothing to do (an offset at or past the row's end -- a table that does not match its prefix)
 __device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefix, int n_rows, int chunk, Row &row, Span &s)
 {
-    const int r = find_row(prefix, n_rows, chunk);
+    const int r = og_find_row(prefix, n_rows, chunk);
     const int64_t *e = rows + (size_t)r * 5;
     row.p = (gfloat *)(uintptr_t)e[0];
     row.g = (const gfloat *)(uintptr_t)e[1];
@@ -61,14 +43,11 @@ __device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefi
     return true;
 }
 
-// The vector frame of a span is anchored on `anchor` (p for the updates, g for the sum of squares): lo is a multiple of four
-// elements, so the first 16-byte aligned element of every chunk sits `head` elements in.
+// The vector frame of a span (table.h) is anchored on `anchor` (p for the updates, g for the sum of squares), given at element lo.
 __device__ __forceinline__ void frame(const gfloat *anchor, Span &s)
 {
-    const int head = (int)(((16u - (unsigned)((uintptr_t)anchor & 15u)) & 15u) >> 2);
-    s.vs = s.lo + head < s.hi ? s.lo + head : s.hi;
-    s.n_vec = (int)((s.hi - s.vs) >> 2);
-    s.tail = s.vs + 4L * s.n_vec;
+    s.f = og_frame(anchor, (int)(s.hi - s.lo), 4);
+    s.vs = s.lo + s.f.head;
 }
 
 __device__ __forceinline__ bool aligned16(const gfloat *q) { return ((uintptr_t)q & 15u) == 0; }
@@ -96,13 +75,11 @@ __device__ __forceinline__ void store4(gfloat *q, bool vec, f4 x)
     }
 }
 
-// The scalar elements of a span, one thread each: the head on threads 0.., the tail on threads 64.. (another wave).  -1: none.
+// The scalar element of this thread as an element of the row, or -1
 __device__ __forceinline__ long edge_element(const Span &s)
 {
-    const int t = threadIdx.x;
-    if (t < (int)(s.vs - s.lo)) return s.lo + t;
-    if (t >= 64 && t - 64 < (int)(s.hi - s.tail)) return s.tail + (t - 64);
-    return -1;
+    const int e = og_frame_edge(s.f, (int)(s.hi - s.lo));
+    return e < 0 ? -1 : s.lo + e;
 }
 
 // ---- sum of squares ------------------------------------------------------------------------------------------------------------
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(OPTIM_THREADS) void grad_sumsq_kernel(const int64_t
     double acc = 0.0;
     if (locate(rows, prefix, n_rows, blockIdx.x, row, s)) {
         frame(row.g + s.lo, s);
-        for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+        for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
             const f4 g = *(const gf4 *)(row.g + s.vs + 4L * k);
             acc += (double)g.x * (double)g.x;
             acc += (double)g.y * (double)g.y;
@@ -282,7 +259,7 @@ __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t 
     frame(row.p + s.lo, s);
     const bool gv = aligned16(row.g + s.vs), mv = aligned16(row.m + s.vs), vv = aligned16(row.v + s.vs);
 #pragma unroll 2
-    for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+    for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
         const long i = s.vs + 4L * k;
         f4 p = *(const gf4 *)(row.p + i);
         const f4 g = load4(row.g + i, gv);
@@ -348,7 +325,7 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
     const bool gv = aligned16(row.g + s.vs), mv = HAS_BUF && aligned16(row.m + s.vs);
     const bool read_buf = HAS_BUF && !a.first;
 #pragma unroll 2
-    for (int k = threadIdx.x; k < s.n_vec; k += OPTIM_THREADS) {
+    for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
         const long i = s.vs + 4L * k;
         f4 p = *(const gf4 *)(row.p + i);
         const f4 g = load4(row.g + i, gv);
@@ -374,15 +351,6 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
     }
 }
 
-int check_table(const char *name, const void *rows, const void *prefix, int n_rows, int chunk_first, int n_chunks)
-{
-    OG_REQUIRE(rows && prefix, OG_EINVAL, "%s: null table", name);
-    OG_REQUIRE(((uintptr_t)rows & 7u) == 0 && ((uintptr_t)prefix & 3u) == 0, OG_EINVAL, "%s: misaligned table", name);
-    OG_REQUIRE(n_rows > 0 && chunk_first >= 0 && n_chunks >= 0, OG_EINVAL, "%s: bad table size (%d rows, chunks %d + %d)", name, n_rows,
-               chunk_first, n_chunks);
-    return OG_OK;
-}
-
 }  // namespace
 
 OG_API int og_optim_chunk_elems(void) { return OPTIM_CHUNK; }
@@ -396,7 +364,7 @@ OG_API int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, i
                              size_t workspace_bytes, void *stream)
 {
     const char *name = "og_grad_sumsq_f32";
-    if (int rc = check_table(name, rows, chunk_prefix, n_rows, 0, n_chunks)) return rc;
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
     OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
     OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
                workspace_bytes, og_optim_workspace_bytes(n_chunks));
@@ -459,7 +427,8 @@ OG_API int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, in
                             float bc2, int adam_w_mode, void *stream)
 {
     const char *name = "og_adam_step_f32";
-    if (int rc = check_table(name, rows, chunk_prefix, n_rows, chunk_first, n_chunks)) return rc;
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
+    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
     OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
     OG_REQUIRE(bc1 > 0.f && bc2 > 0.f, OG_EINVAL, "%s: bias corrections must be positive (bc1 %g, bc2 %g)", name, bc1, bc2);
     if (n_chunks == 0) return OG_OK;
@@ -474,7 +443,8 @@ OG_API int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int
                            float lr, float mom, float wd, int first, void *stream)
 {
     const char *name = "og_sgd_step_f32";
-    if (int rc = check_table(name, rows, chunk_prefix, n_rows, chunk_first, n_chunks)) return rc;
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
+    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
     OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
     if (n_chunks == 0) return OG_OK;
     const SgdArgs a{lr, mom, wd, first != 0};

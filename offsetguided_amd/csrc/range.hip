@@ -8,7 +8,7 @@
 // over one device body: a table of tensors in device memory (og_range_stats: every weight of a model in one launch) and one tensor
 // given as kernel arguments (og_range_probe: an activation inside a graph capture).  tests/range_common.py restates the nine words
 // in numpy; the GPU test asks for equality.
-#include "og_common.h"
+#include "table.h"
 
 namespace {
 
@@ -17,12 +17,6 @@ constexpr int RANGE_CHUNK = 8192;            // elements of one chunk: 16 KB of 
 constexpr int RANGE_PROBE_MAX_WG = 1024;     // og_range_probe: at most this many workgroups, each strides over the chunks
 constexpr int RANGE_ROW_WORDS = 4;
 constexpr int SRC_F32 = 0, SRC_F16 = 1, SRC_BF16 = 2;
-
-typedef __attribute__((address_space(1))) unsigned char gu8;
-typedef __attribute__((address_space(1))) unsigned short gu16;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u4 gu4;
 
 constexpr uint32_t F32_INF = 0x7f800000u;
 constexpr uint32_t F16_OVER = 0x477ff000u;       // 65520: the smallest magnitude that rounds to fp16's inf
@@ -103,31 +97,25 @@ __device__ __forceinline__ void classify_word(uint32_t w, Acc &a)
 template <bool F16, int S>
 __device__ __forceinline__ long scan_chunks(const gu8 *base, long numel, long first, long stride, Acc &a)
 {
-    constexpr int SHIFT = S == SRC_F32 ? 2 : 1, PER = 16 >> SHIFT;
+    constexpr int SHIFT = S == SRC_F32 ? 2 : 1;
     const long n_chunks = (numel + RANGE_CHUNK - 1) / RANGE_CHUNK;
-    const int t = threadIdx.x;
     long seen = 0;
     for (long c = first; c < n_chunks; c += stride) {
         const long lo = c * RANGE_CHUNK;
         const int n = numel - lo < RANGE_CHUNK ? (int)(numel - lo) : RANGE_CHUNK;
         seen += n;
         const gu8 *p = base + (lo << SHIFT);
-        int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> SHIFT);
-        head = head < n ? head : n;
-        const int n_vec = (n - head) / PER, tail = head + n_vec * PER;
-        const gu4 *v = (const gu4 *)(p + ((long)head << SHIFT));       // 16-byte aligned; every vector lies inside [lo, lo + n)
+        const OgFrame f = og_frame(p, n, 1 << SHIFT);
+        const gu4 *v = (const gu4 *)(p + ((long)f.head << SHIFT));     // 16-byte aligned; every vector lies inside [lo, lo + n)
 #pragma unroll 4
-        for (int k = t; k < n_vec; k += RANGE_THREADS) {
+        for (int k = threadIdx.x; k < f.n_vec; k += RANGE_THREADS) {
             const u4 q = v[k];
             classify_word<F16, S>(q.x, a);
             classify_word<F16, S>(q.y, a);
             classify_word<F16, S>(q.z, a);
             classify_word<F16, S>(q.w, a);
         }
-        // the scalar edges: the head on threads 0.., the tail on threads 64.. (another wave); fewer than PER elements each
-        int e = -1;
-        if (t < head) e = t;
-        if (t >= 64 && t - 64 < n - tail) e = tail + t - 64;
+        const int e = og_frame_edge(f, n);
         if (e >= 0) {
             if (S == SRC_F32) classify32<F16>(((const gu32 *)p)[e], a);
             else classify16<F16>(((const gu16 *)p)[e], a);
@@ -177,23 +165,11 @@ __device__ __forceinline__ void range_body(const gu8 *base, long numel, int styp
     }
 }
 
-// Row of workgroup `wg`: the largest r < n_rows with prefix[r] <= wg (prefix[n_rows] is the total): rows without workgroups are passed over
-__device__ __forceinline__ int find_row(const int32_t *prefix, int n_rows, int wg)
-{
-    int lo = 0, hi = n_rows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 template <bool F16>
 __global__ __launch_bounds__(RANGE_THREADS) void range_table_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
                                                                     int n_rows, unsigned long long *stats)
 {
-    const int r = find_row(prefix, n_rows, blockIdx.x);
+    const int r = og_find_row(prefix, n_rows, blockIdx.x);
     const int64_t *e = rows + (size_t)r * RANGE_ROW_WORDS;
     const long numel = e[1], out = e[3];
     const int first = (int)blockIdx.x - prefix[r], share = prefix[r + 1] - prefix[r];
@@ -215,10 +191,8 @@ OG_API int og_range_stats(const int64_t *rows, const int32_t *wg_prefix, int n_r
                           void *stream)
 {
     const char *name = "og_range_stats";
-    OG_REQUIRE(rows && wg_prefix && stats, OG_EINVAL, "%s: null table or stats", name);
-    OG_REQUIRE(((uintptr_t)rows & 7u) == 0 && ((uintptr_t)wg_prefix & 3u) == 0 && ((uintptr_t)stats & 7u) == 0, OG_EINVAL,
-               "%s: misaligned table or stats", name);
-    OG_REQUIRE(n_rows > 0 && n_workgroups >= 0, OG_EINVAL, "%s: bad table size (%d rows, %d workgroups)", name, n_rows, n_workgroups);
+    if (int rc = og_check_table(name, rows, wg_prefix, n_rows, n_workgroups)) return rc;
+    OG_REQUIRE(stats && ((uintptr_t)stats & 7u) == 0, OG_EINVAL, "%s: null or misaligned stats", name);
     OG_REQUIRE(target == OG_RANGE_F16 || target == OG_RANGE_BF16, OG_EINVAL, "%s: target type %d is neither fp16 nor bf16", name, target);
     if (n_workgroups == 0) return OG_OK;
     unsigned long long *out = (unsigned long long *)stats;

@@ -39,7 +39,7 @@ import torch
 import torch.nn.functional as F
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from .. import _lib
+from .. import _lib, _table
 from .hourglass_104 import ConvBlock, HourglassLevel, Residual
 
 
@@ -667,7 +667,7 @@ class _Layers:
         self.heads_b, self.head_channels = None, None
         self.stage, self.dtype, self.device, self.fused = stage, dtype, device, fused
         self.module = weakref.ref(model)      # the module whose CURRENT weights the bundle holds (moved by refresh)
-        self._fold_table, self._fold_slots, self._finalizer = None, [], None
+        self._fold_table, self._fold_pool, self._finalizer = None, _table.Pool(), None
         # the caller's module is only read: weights are folded from it onto the engine's device (no .to(), no .eval())
         _issuer.build_device = device
         _issuer.names = {id(m): n for n, m in model.named_modules()}

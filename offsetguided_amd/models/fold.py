@@ -1,11 +1,9 @@
 """The HIP side of InferenceEngine.refresh: the table of og_fold_bn_w16 (include/og_decoder.h, "weight refresh"; csrc/fold.hip) for a
-weight bundle (models/engine.py:_Layers) and its one launch.  The table is filled in pinned memory and copied once, as
-optim._DeviceOptimizer._upload does: a pinned slot is written again only after the copy that read it has finished."""
+weight bundle (models/engine.py:_Layers) and its one launch.  The table is packed and uploaded by _table.py."""
 import numpy as np
 import torch
 
-from .. import _lib
-from ..optim import _TableSlot
+from .. import _lib, _table
 
 SLAB_ELEMS = 16384      # weights one workgroup folds: whole output channels, at least one
 
@@ -53,26 +51,15 @@ def fold_bundle(layers, convs, pairs, events=None):
         table[i] = [w.data_ptr(), *(v.data_ptr() if v is not None else 0 for v in vecs), c.w.data_ptr(), c.b32.data_ptr(),
                     c.b.data_ptr(), cout, cin, kh * kw, channels_last, eps, index[id(partner)] if partner is not None else -1, slab]
         groups[i] = -(-cout // slab)
-    prefix = np.zeros(len(convs) + 1, np.int32)
-    np.cumsum(groups, out=prefix[1:])
-    raw = np.concatenate([table.reshape(-1).view(np.uint8), prefix.view(np.uint8)])
-    slot = next((s for s in layers._fold_slots if s.buf.numel() >= raw.size and s.free()), None)
-    if slot is None:
-        slot = _TableSlot(raw.size)
-        layers._fold_slots.append(slot)
-    slot.buf[:raw.size].copy_(torch.from_numpy(raw))
+    raw, prefix, prefix_at = _table.pack(table, groups)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        if layers._fold_table is None or layers._fold_table.numel() != raw.size:
-            layers._fold_table = torch.empty(raw.size, dtype=torch.uint8, device=dev)
-        layers._fold_table.copy_(slot.buf[:raw.size], non_blocking=True)
-        slot.event = torch.cuda.Event()
-        slot.event.record(stream)
+        layers._fold_table = _table.upload(raw, dev, layers._fold_pool, out=layers._fold_table)
         rows = layers._fold_table.data_ptr()
         if events is not None:
             events.append((_lib.TimingEvent(), _lib.TimingEvent()))
             events[-1][0].record(stream)
-        _lib.check(lib.og_fold_bn_w16(rows, rows + 8 * table.size, len(convs), int(prefix[-1]), int(layers.dtype == torch.float16),
+        _lib.check(lib.og_fold_bn_w16(rows, rows + prefix_at, len(convs), int(prefix[-1]), int(layers.dtype == torch.float16),
                                       _lib.stream_ptr(dev)), lib)
         if events is not None:
             events[-1][1].record(stream)

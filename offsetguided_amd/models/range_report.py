@@ -1,20 +1,19 @@
 """Range report: what the engine's 16-bit type does to weights and activations, counted on the device (include/og_decoder.h, "range
 report"; csrc/range.hip).  A stats row is nine int64 words -- n, nan, inf, over, zero, flush, sub, max, min -- that every launch
-accumulates into.  range_stats queues ONE launch over a list of tensors (the table is filled in pinned memory and copied once, as
-models/fold.py does) and does not wait; probe queues one launch on one tensor with its address as a kernel argument (the form a graph
+accumulates into.  range_stats queues ONE launch over a list of tensors (the table is packed and uploaded by _table.py) and does
+not wait; probe queues one launch on one tensor with its address as a kernel argument (the form a graph
 capture needs); decode is the one place that reads anything back."""
 import numpy as np
 import torch
 
-from .. import _lib
-from ..optim import _TableSlot
+from .. import _lib, _table
 
 WORDS = 9
 NAMES = ('n', 'nan', 'inf', 'over', 'zero', 'flush', 'sub', 'max', 'min')
 TYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 PROBE_MAX_WG = 1024      # workgroups of one tensor at most: beyond that each strides over several chunks (one set of atomics per workgroup)
 _F32_INF = 0x7f800000
-_slots = []
+_pool = _table.Pool()
 
 
 def _target(dtype):
@@ -69,21 +68,10 @@ def range_stats(tensors, target_dtype, rows=None, out=None):
         for i, (t, code, r) in enumerate(zip(tensors, codes, rows)):
             table[i] = [t.data_ptr(), t.numel(), code, r]
             groups[i] = min(-(-t.numel() // chunk), PROBE_MAX_WG)
-        prefix = np.zeros(len(tensors) + 1, np.int32)
-        np.cumsum(groups, out=prefix[1:])
-        raw = np.concatenate([table.reshape(-1).view(np.uint8), prefix.view(np.uint8)])
-        slot = next((s for s in _slots if s.buf.numel() >= raw.size and s.free()), None)
-        if slot is None:
-            slot = _TableSlot(raw.size)
-            _slots.append(slot)
-        slot.buf[:raw.size].copy_(torch.from_numpy(raw))
-        stream = torch.cuda.current_stream(dev)
-        dev_table = torch.empty(raw.size, dtype=torch.uint8, device=dev)       # stream-ordered: free to go once the launch is queued
-        dev_table.copy_(slot.buf[:raw.size], non_blocking=True)
-        slot.event = torch.cuda.Event()
-        slot.event.record(stream)
+        raw, prefix, prefix_at = _table.pack(table, groups)
+        dev_table = _table.upload(raw, dev, _pool)       # a new tensor, stream-ordered: free to go once the launch is queued
         at = dev_table.data_ptr()
-        _lib.check(lib.og_range_stats(at, at + 8 * table.size, len(tensors), int(prefix[-1]), target, _lib.ptr(out),
+        _lib.check(lib.og_range_stats(at, at + prefix_at, len(tensors), int(prefix[-1]), target, _lib.ptr(out),
                                       _lib.stream_ptr(dev)), lib)
     return out
 

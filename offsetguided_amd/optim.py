@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _table
 
 
 def _same_layout(a, b):
@@ -34,17 +34,6 @@ def _dense(t):
             return False
         expected *= size
     return True
-
-
-class _TableSlot:
-    """One pinned staging area of the tensor table; `event` is recorded behind the copy that reads it."""
-
-    def __init__(self, nbytes):
-        self.buf = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
-        self.event = None
-
-    def free(self):
-        return self.event is None or self.event.query()
 
 
 class DeviceLossScaler:
@@ -143,8 +132,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         self._signature = None    # what the device table was built from
         self._table = None
         self._segments = []       # (group index, key, first chunk, chunk count)
-        self._n_rows = self._n_chunks = 0
-        self._slots = []
+        self._n_rows = self._n_chunks = self._prefix_at = 0
+        self._pool = _table.Pool()
         self._ws = None
 
     # ---- the state block ------------------------------------------------------------------------------------------------------
@@ -260,24 +249,13 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         if signature == self._signature:
             return
         table = np.array(rows, dtype=np.int64).reshape(-1, 5)
-        prefix = np.zeros(len(rows) + 1, dtype=np.int32)
-        np.cumsum(-(-table[:, 4] // chunk), out=prefix[1:])
+        raw, prefix, self._prefix_at = _table.pack(table, -(-table[:, 4] // chunk))
         self._segments = []
         for i, key in enumerate(keys):
             if i == 0 or key != keys[i - 1]:
                 self._segments.append([key[0], key[1], int(prefix[i]), 0])
             self._segments[-1][3] = int(prefix[i + 1]) - self._segments[-1][2]
-        raw = np.concatenate([table.reshape(-1).view(np.uint8), prefix.view(np.uint8)])
-        # pinned slots (decoder.factory._HostSlot): one is written again only after the copy that read it has finished
-        slot = next((s for s in self._slots if s.buf.numel() >= raw.size and s.free()), None)
-        if slot is None:
-            slot = _TableSlot(raw.size * 2)
-            self._slots.append(slot)
-        slot.buf[:raw.size].copy_(torch.from_numpy(raw))
-        self._table = torch.empty(raw.size, dtype=torch.uint8, device=dev)
-        self._table.copy_(slot.buf[:raw.size], non_blocking=True)
-        slot.event = torch.cuda.Event()
-        slot.event.record(torch.cuda.current_stream(dev))
+        self._table = _table.upload(raw, dev, self._pool)
         self._n_rows, self._n_chunks = len(rows), int(prefix[-1])
         self._signature = signature
 
@@ -306,7 +284,7 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             ws = self._workspace(dev, lib)
             self._upload(entries, dev, lib)
             stream = _lib.stream_ptr(dev)
-            rows, prefix = self._table.data_ptr(), self._table.data_ptr() + 40 * self._n_rows
+            rows, prefix = self._table.data_ptr(), self._table.data_ptr() + self._prefix_at
             state_ptr = None
             if loss is not None or math.isfinite(max_grad_norm) or scaler is not None:
                 if loss is not None:

@@ -93,6 +93,22 @@ def test_both_entry_points_word_for_word(dev, source, target):
     assert np.array_equal(twice[:, :7], 2 * want[:, :7]) and np.array_equal(twice[:, 7:], want[:, 7:])
 
 
+def test_table_rows_without_workgroups_between_the_others(dev):
+    """Empty rows in the middle and at the end of a table (the case above has them only at its front): the smallest table in which a
+    wrong bisection hands a workgroup a neighbouring row."""
+    chunk = _lib.load().og_range_chunk_elems()
+    lengths = [9, 0, 0, chunk + 1, 0]
+    data = [_bits('f32', n, 70 + i) for i, n in enumerate(lengths)]
+    placed = [_place(b, 1 + i % 3, 'f32', dev) for i, b in enumerate(data)]
+    with no_host_wait():
+        got = range_report.range_stats([v for _, v in placed], torch.float16)
+    got = got.cpu().numpy()
+    want = np.stack([rg.stats_ref(b, 'f32', 'f16') for b in data])
+    assert want[:, 0].tolist() == lengths and not want[[1, 2, 4]].any()
+    for n, g, w in zip(lengths, got, want):
+        assert np.array_equal(g, w), f'length {n}: {dict(zip(rg.NAMES, g))} != {dict(zip(rg.NAMES, w))}'
+
+
 def test_refused_types(dev):
     lib = _lib.load()
     x = torch.zeros(64, dtype=torch.float16, device=dev)
