@@ -813,10 +813,28 @@ int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspa
  *     mom != 0, not first:  t = mom * buf;  buf = t + ge
  *     mom == 0:             buf stands for ge; no buffer is read or written
  *     s = lr * buf;   p' = p - s
+ * Weight average (an exponential moving average of the weights, optim.ModelEma; the reference has none: this text is the
+ * specification).  og_adam_step_ema_f32 / og_sgd_step_ema_f32 take the arguments of og_adam_step_f32 / og_sgd_step_f32 and
+ * `ema`, device memory int64[n_rows] in step with `rows`: the address of the row's average e, or 0 for "this row has none" -- fp32,
+ * dense, in the element order of p, 4-byte aligned, any offset beyond that (16-byte accesses where e's own address allows, decided
+ * per tensor as for g, m, v; the frame stays p's) -- and omd = 1 - decay of this step, computed by the host in double and rounded to
+ * fp32 once.  The p, m, v arithmetic is the list above, unchanged; behind it, with p' the value that is stored, per element, every
+ * line ONE individually rounded fp32 operation:
+ *     d = p' - e;   t = omd * d;   e' = e + t
+ *   A row with ema[r] == 0 runs exactly the plain update and nothing else is read or written.  The average follows p' on EVERY step,
+ *   a dropped or overflow step (scale == 0) included: such a step is still the zero-gradient update here (moments decay, weight decay
+ *   acts), and the average tracks the weights the model actually has.  A non-finite p' poisons e: not guarded against.  omd == 0
+ *   leaves e as it is; omd == 1 gives e + (p' - e), which need not be p'.  og_adam_step_f32 / og_sgd_step_f32 launch the same kernels'
+ *   instantiation without the average.
+ * og_ema_lerp_f32: the same three lines with x for p', for the tensors no update touches in a step (BatchNorm running statistics,
+ * frozen parameters, a parameter without a gradient).  Table: `rows` int64[n_rows][3], one row (e, x, numel) -- two device addresses
+ * of dense fp32 data in one common element order, 4-byte aligned, any offset beyond that; e is read and written, x read -- and the
+ * chunk prefix as above, chunks of og_optim_chunk_elems() elements.  The frame is e's; x takes 16-byte loads where its address allows.
  * All: no allocation, no synchronisation, graph-capturable; n_chunks == 0 launches nothing (og_step_scale_f32 always launches).
  * OG_EINVAL (nothing launched): a null or misaligned table, workspace, loss or state; n_rows <= 0; a negative chunk count; a NaN
- * max_norm or loss_limit; bc1 or bc2 not positive.  OG_ENOSPC: workspace_bytes too small.  The table's contents are device memory
- * and are not validated: its builder answers for addresses and counts. */
+ * max_norm or loss_limit; bc1 or bc2 not positive; for the _ema entry points and og_ema_lerp_f32 a null or misaligned (8 bytes) `ema`
+ * table, omd outside [0, 1] or NaN.  OG_ENOSPC: workspace_bytes too small.  The tables' contents are device memory and are not
+ * validated: their builder answers for addresses and counts. */
 int og_optim_chunk_elems(void);
 size_t og_optim_workspace_bytes(int n_chunks);
 int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, void *workspace,
@@ -831,6 +849,12 @@ int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_row
                      void *stream);
 int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
                     float lr, float mom, float wd, int first, void *stream);
+int og_adam_step_ema_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                         float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1, float bc2,
+                         int adam_w_mode, const int64_t *ema, float omd, void *stream);
+int og_sgd_step_ema_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                        float lr, float mom, float wd, int first, const int64_t *ema, float omd, void *stream);
+int og_ema_lerp_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, float omd, void *stream);
 
 /* ---- weight refresh: BatchNorm fold + 16-bit cast of every layer in one launch (models/engine.py: InferenceEngine.refresh;
  * csrc/fold.hip) ----  What an engine computes with torch ops when it is built (_fold, .to(dtype), channels-last), written into the

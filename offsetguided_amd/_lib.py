@@ -130,6 +130,9 @@ SIGNATURES = {
     "og_step_scale_amp_f32": (_i, [_i, _vp, _f, _f, _vp, _i, _f, _i, _f, _f, _vp, _sz, _vp]),
     "og_adam_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp]),
     "og_sgd_step_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp]),
+    "og_adam_step_ema_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp, _f, _vp]),
+    "og_sgd_step_ema_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _i, _vp, _f, _vp]),
+    "og_ema_lerp_f32": (_i, [_vp, _vp, _i, _i, _f, _vp]),
     "og_fold_row_words": (_i, []),
     "og_fold_bn_w16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "og_range_chunk_elems": (_i, []),
@@ -169,7 +172,7 @@ def load():
             raise ImportError(f"{LIB_PATH}: ABI version {lib.og_abi_version()} != {ABI_VERSION}; rebuild with "
                               "`python -m offsetguided_amd.build --force`")
         for name, (res, args) in SIGNATURES.items():
-            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32, og_oks_*, og_coco_*: the ABI only grew) -- a library built before
+            # entry points added without a version change (og_scale_accumulate_f32, og_scored_offset_f32, og_oks_*, og_coco_*, og_*_ema_f32: the ABI only grew) -- a library built before
             # them says so here instead of with a bare AttributeError
             if not hasattr(lib, name):
                 raise ImportError(f"{LIB_PATH} lacks {name}: stale build; rebuild with `python -m offsetguided_amd.build --force`")

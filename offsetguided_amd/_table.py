@@ -33,14 +33,16 @@ class Pool:
         return slot
 
 
-def pack(table, counts):
-    """table: int64 (n_rows, words); counts: the workgroups of every row (0: the kernel passes the row over).
-    -> (raw, prefix, offset): the table's bytes (uint8: the rows, then the prefix), the int32 prefix [0, counts[0], counts[0] +
-    counts[1], ...] and the byte offset of the prefix inside raw (a multiple of 8: the rows are whole int64 words)."""
+def pack(table, counts, extra=None):
+    """table: int64 (n_rows, words); counts: the workgroups of every row (0: the kernel passes the row over); extra: int64 words that
+    travel between the rows and the prefix (a column a kernel takes as a table of its own: at byte 8 * table.size of raw).
+    -> (raw, prefix, offset): the table's bytes (uint8: the rows, the extra words, then the prefix), the int32 prefix [0, counts[0],
+    counts[0] + counts[1], ...] and the byte offset of the prefix inside raw (a multiple of 8: whole int64 words lie before it)."""
     table = np.ascontiguousarray(table, dtype=np.int64)
     prefix = np.zeros(table.shape[0] + 1, dtype=np.int32)
     np.cumsum(counts, out=prefix[1:])
-    return np.concatenate([table.reshape(-1).view(np.uint8), prefix.view(np.uint8)]), prefix, 8 * table.size
+    words = [table.reshape(-1)] if extra is None else [table.reshape(-1), np.ascontiguousarray(extra, dtype=np.int64).reshape(-1)]
+    return np.concatenate([w.view(np.uint8) for w in words] + [prefix.view(np.uint8)]), prefix, 8 * sum(w.size for w in words)
 
 
 def upload(raw, device, pool, out=None):

@@ -4,7 +4,9 @@
 // 16-byte loads and stores wherever a tensor's address allows them, a scalar head and tail where it does not.  The arithmetic is the
 // header's list of individually rounded fp32 operations (the library is built with -ffp-contract=off, correctly rounded divide and
 // sqrt): tests/optim_common.py restates it in numpy and the GPU tests compare bit for bit.  No float atomics anywhere: the sum of
-// squares goes through per-chunk partials in double and a fixed-order reduction.
+// squares goes through per-chunk partials in double and a fixed-order reduction.  The updates are templates on EMA: with it a row
+// that has an average (the `ema` address table) folds e' = e + omd * (p' - e) into the store of p', 8 B per parameter more and no
+// second pass over p; og_ema_lerp_f32 is the same rule over the tensors no update touches.
 #include "table.h"
 
 namespace {
@@ -20,6 +22,7 @@ struct Row {
     gfloat *m;
     gfloat *v;
     long n;
+    int index;         // the row's place in the table (and in the `ema` address table beside it)
 };
 
 struct Span {          // what a workgroup owns: elements [lo, hi) of its row; vectors of four from element vs, f.n_vec of them
@@ -28,6 +31,14 @@ struct Span {          // what a workgroup owns: elements [lo, hi) of its row; v
 };
 
 // false: nothing to do (an offset at or past the row's end -- a table that does not match its prefix)
+__device__ __forceinline__ bool span_of(const int32_t *prefix, int r, int chunk, long n, Span &s)
+{
+    s.lo = (long)(chunk - prefix[r]) * OPTIM_CHUNK;
+    if (s.lo < 0 || s.lo >= n) return false;
+    s.hi = n - s.lo > OPTIM_CHUNK ? s.lo + OPTIM_CHUNK : n;
+    return true;
+}
+
 __device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefix, int n_rows, int chunk, Row &row, Span &s)
 {
     const int r = og_find_row(prefix, n_rows, chunk);
@@ -37,10 +48,8 @@ __device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefi
     row.m = (gfloat *)(uintptr_t)e[2];
     row.v = (gfloat *)(uintptr_t)e[3];
     row.n = e[4];
-    s.lo = (long)(chunk - prefix[r]) * OPTIM_CHUNK;
-    if (s.lo < 0 || s.lo >= row.n) return false;
-    s.hi = row.n - s.lo > OPTIM_CHUNK ? s.lo + OPTIM_CHUNK : row.n;
-    return true;
+    row.index = r;
+    return span_of(prefix, r, chunk, row.n, s);
 }
 
 // The vector frame of a span (table.h) is anchored on `anchor` (p for the updates, g for the sum of squares), given at element lo.
@@ -249,8 +258,33 @@ __device__ __forceinline__ void adam_element(const AdamArgs &a, float scale, flo
     p = p - s;
 }
 
+// The average behind an update (header: "weight average"): x is p' as it is stored, three individually rounded operations.
+__device__ __forceinline__ float ema_element(float omd, float x, float e)
+{
+    const float d = x - e;
+    const float t = omd * d;
+    return e + t;
+}
+
+__device__ __forceinline__ void ema4(float omd, const f4 &x, f4 &e)
+{
+    e.x = ema_element(omd, x.x, e.x);
+    e.y = ema_element(omd, x.y, e.y);
+    e.z = ema_element(omd, x.z, e.z);
+    e.w = ema_element(omd, x.w, e.w);
+}
+
+// The row's average, or null: without EMA the table is never read
+template <bool EMA>
+__device__ __forceinline__ gfloat *average_of(const int64_t *ema, const Row &row)
+{
+    return EMA ? (gfloat *)(uintptr_t)ema[row.index] : nullptr;
+}
+
+template <bool EMA>
 __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
-                                                                  int n_rows, int chunk_first, const float *__restrict__ state, AdamArgs a)
+                                                                  int n_rows, int chunk_first, const float *__restrict__ state, AdamArgs a,
+                                                                  const int64_t *__restrict__ ema, float omd)
 {
     Row row;
     Span s;
@@ -258,6 +292,8 @@ __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t 
     const float scale = state ? state[0] : 1.f;
     frame(row.p + s.lo, s);
     const bool gv = aligned16(row.g + s.vs), mv = aligned16(row.m + s.vs), vv = aligned16(row.v + s.vs);
+    gfloat *const avg = average_of<EMA>(ema, row);
+    const bool has_avg = EMA && avg != nullptr, ev = has_avg && aligned16(avg + s.vs);
 #pragma unroll 2
     for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
         const long i = s.vs + 4L * k;
@@ -265,6 +301,8 @@ __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t 
         const f4 g = load4(row.g + i, gv);
         f4 m = load4(row.m + i, mv);
         f4 v = load4(row.v + i, vv);
+        f4 e = {0.f, 0.f, 0.f, 0.f};
+        if (has_avg) e = load4(avg + i, ev);
 #define ADAM_LANE(c)                                  \
     {                                                 \
         float p_ = p.c, m_ = m.c, v_ = v.c;           \
@@ -276,6 +314,10 @@ __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t 
         *(gf4 *)(row.p + i) = p;
         store4(row.m + i, mv, m);
         store4(row.v + i, vv, v);
+        if (has_avg) {
+            ema4(omd, p, e);
+            store4(avg + i, ev, e);
+        }
     }
     const long e = edge_element(s);
     if (e >= 0) {
@@ -284,6 +326,9 @@ __global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t 
         row.p[e] = p;
         row.m[e] = m;
         row.v[e] = v;
+        if (has_avg) {
+            avg[e] = ema_element(omd, p, avg[e]);
+        }
     }
 }
 
@@ -313,9 +358,10 @@ __device__ __forceinline__ void sgd_element(const SgdArgs &a, float scale, float
     p = p - s;
 }
 
-template <bool HAS_BUF>
+template <bool HAS_BUF, bool EMA>
 __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
-                                                                 int n_rows, int chunk_first, const float *__restrict__ state, SgdArgs a)
+                                                                 int n_rows, int chunk_first, const float *__restrict__ state, SgdArgs a,
+                                                                 const int64_t *__restrict__ ema, float omd)
 {
     Row row;
     Span s;
@@ -324,6 +370,8 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
     frame(row.p + s.lo, s);
     const bool gv = aligned16(row.g + s.vs), mv = HAS_BUF && aligned16(row.m + s.vs);
     const bool read_buf = HAS_BUF && !a.first;
+    gfloat *const avg = average_of<EMA>(ema, row);
+    const bool has_avg = EMA && avg != nullptr, ev = has_avg && aligned16(avg + s.vs);
 #pragma unroll 2
     for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
         const long i = s.vs + 4L * k;
@@ -331,6 +379,8 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
         const f4 g = load4(row.g + i, gv);
         f4 m = {0.f, 0.f, 0.f, 0.f};
         if (read_buf) m = load4(row.m + i, mv);
+        f4 e = {0.f, 0.f, 0.f, 0.f};
+        if (has_avg) e = load4(avg + i, ev);
 #define SGD_LANE(c)                                       \
     {                                                     \
         float p_ = p.c, m_ = m.c;                         \
@@ -341,6 +391,10 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
 #undef SGD_LANE
         *(gf4 *)(row.p + i) = p;
         if (HAS_BUF) store4(row.m + i, mv, m);
+        if (has_avg) {
+            ema4(omd, p, e);
+            store4(avg + i, ev, e);
+        }
     }
     const long e = edge_element(s);
     if (e >= 0) {
@@ -348,6 +402,36 @@ __global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *
         sgd_element<HAS_BUF>(a, scale, p, row.g[e], m);
         row.p[e] = p;
         if (HAS_BUF) row.m[e] = m;
+        if (has_avg) {
+            avg[e] = ema_element(omd, p, avg[e]);
+        }
+    }
+}
+
+// ---- the average of what no update touches ---------------------------------------------------------------------------------------
+// rows (e, x, numel); the vector frame is anchored on e, the tensor that is written.
+__global__ __launch_bounds__(OPTIM_THREADS) void ema_lerp_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
+                                                                 int n_rows, float omd)
+{
+    const int r = og_find_row(prefix, n_rows, blockIdx.x);
+    const int64_t *w = rows + (size_t)r * 3;
+    gfloat *const avg = (gfloat *)(uintptr_t)w[0];
+    const gfloat *const x = (const gfloat *)(uintptr_t)w[1];
+    Span s;
+    if (!span_of(prefix, r, blockIdx.x, w[2], s)) return;
+    frame(avg + s.lo, s);
+    const bool xv = aligned16(x + s.vs);
+#pragma unroll 2
+    for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
+        const long i = s.vs + 4L * k;
+        f4 e = *(const gf4 *)(avg + i);
+        const f4 src = load4(x + i, xv);
+        ema4(omd, src, e);
+        *(gf4 *)(avg + i) = e;
+    }
+    const long i = edge_element(s);
+    if (i >= 0) {
+        avg[i] = ema_element(omd, x[i], avg[i]);
     }
 }
 
@@ -422,19 +506,70 @@ OG_API int og_step_scale_amp_f32(int n_chunks, const float *loss, float loss_lim
     return OG_OK;
 }
 
+// Both forms of an update's entry point: ema == nullptr launches the instantiation without the average.
+static int adam_step(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
+                     int n_chunks, const void *state, const AdamArgs &a, const int64_t *ema, float omd, void *stream)
+{
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
+    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
+    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
+    OG_REQUIRE(a.bc1 > 0.f && a.bc2 > 0.f, OG_EINVAL, "%s: bias corrections must be positive (bc1 %g, bc2 %g)", name, a.bc1, a.bc2);
+    if (with_ema) {
+        OG_REQUIRE(ema && ((uintptr_t)ema & 7u) == 0, OG_EINVAL, "%s: null or misaligned ema table", name);
+        OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
+    }
+    if (n_chunks == 0) return OG_OK;
+    if (with_ema)
+        hipLaunchKernelGGL(adam_step_kernel<true>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                           chunk_first, static_cast<const float *>(state), a, ema, omd);
+    else
+        hipLaunchKernelGGL(adam_step_kernel<false>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
+                           chunk_first, static_cast<const float *>(state), a, ema, omd);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
 OG_API int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks,
                             const void *state, float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1,
                             float bc2, int adam_w_mode, void *stream)
 {
-    const char *name = "og_adam_step_f32";
+    const AdamArgs a{lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, adam_w_mode != 0};
+    return adam_step("og_adam_step_f32", false, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, nullptr, 0.f, stream);
+}
+
+OG_API int og_adam_step_ema_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks,
+                                const void *state, float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                                float bc2, int adam_w_mode, const int64_t *ema, float omd, void *stream)
+{
+    const AdamArgs a{lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, adam_w_mode != 0};
+    return adam_step("og_adam_step_ema_f32", true, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
+}
+
+template <bool EMA>
+static void sgd_launch(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
+                       const SgdArgs &a, const int64_t *ema, float omd, void *stream)
+{
+    if (a.mom != 0.f)
+        hipLaunchKernelGGL((sgd_step_kernel<true, EMA>), dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix,
+                           n_rows, chunk_first, static_cast<const float *>(state), a, ema, omd);
+    else
+        hipLaunchKernelGGL((sgd_step_kernel<false, EMA>), dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix,
+                           n_rows, chunk_first, static_cast<const float *>(state), a, ema, omd);
+}
+
+static int sgd_step(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
+                    int n_chunks, const void *state, const SgdArgs &a, const int64_t *ema, float omd, void *stream)
+{
     if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
     OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
     OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
-    OG_REQUIRE(bc1 > 0.f && bc2 > 0.f, OG_EINVAL, "%s: bias corrections must be positive (bc1 %g, bc2 %g)", name, bc1, bc2);
+    if (with_ema) {
+        OG_REQUIRE(ema && ((uintptr_t)ema & 7u) == 0, OG_EINVAL, "%s: null or misaligned ema table", name);
+        OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
+    }
     if (n_chunks == 0) return OG_OK;
-    const AdamArgs a{lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, adam_w_mode != 0};
-    hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
-                       chunk_first, static_cast<const float *>(state), a);
+    if (with_ema) sgd_launch<true>(rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
+    else sgd_launch<false>(rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }
@@ -442,18 +577,24 @@ OG_API int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, in
 OG_API int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
                            float lr, float mom, float wd, int first, void *stream)
 {
-    const char *name = "og_sgd_step_f32";
-    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
-    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
-    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
-    if (n_chunks == 0) return OG_OK;
     const SgdArgs a{lr, mom, wd, first != 0};
-    if (mom != 0.f)
-        hipLaunchKernelGGL(sgd_step_kernel<true>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
-                           chunk_first, static_cast<const float *>(state), a);
-    else
-        hipLaunchKernelGGL(sgd_step_kernel<false>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
-                           chunk_first, static_cast<const float *>(state), a);
+    return sgd_step("og_sgd_step_f32", false, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, nullptr, 0.f, stream);
+}
+
+OG_API int og_sgd_step_ema_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks,
+                               const void *state, float lr, float mom, float wd, int first, const int64_t *ema, float omd, void *stream)
+{
+    const SgdArgs a{lr, mom, wd, first != 0};
+    return sgd_step("og_sgd_step_ema_f32", true, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
+}
+
+OG_API int og_ema_lerp_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, float omd, void *stream)
+{
+    const char *name = "og_ema_lerp_f32";
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
+    OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
+    if (n_chunks == 0) return OG_OK;
+    hipLaunchKernelGGL(ema_lerp_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows, omd);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }

@@ -66,6 +66,9 @@ def evaluate_cli(argv=None):
     parser.add_argument('--loader-workers', default=8, type=int)
     parser.add_argument('--all-images', default=False, action='store_true')
     parser.add_argument('--resume', '-r', action='store_true', default=False, help='load --checkpoint-whole')
+    parser.add_argument('--use-ema', action='store_true', default=False,
+                        help="with --resume: load the averaged weights of the checkpoint (its ema_state_dict, written by train_dist "
+                             '--ema-decay) instead of the raw ones; a checkpoint without them is an error')
     parser.add_argument('--checkpoint-path', '-p', default='link2checkpoints_storage')
     parser.add_argument('--show-detected-poses', action='store_true', default=False,
                         help="paint every batch's poses over the network-input images on the device (visualization.draw_poses) and "
@@ -93,6 +96,8 @@ def evaluate_cli(argv=None):
     g.add_argument('--channels-last', default=False, action='store_true')
     g.add_argument('--print-freq', '-f', default=10, type=int, metavar='N')
     args = parser.parse_args(argv)
+    if args.use_ema and not args.resume:
+        parser.error('--use-ema loads the averaged weights of a checkpoint: add --resume')
     try:
         validate_test_scales(args.test_scales, args.fixed_height, args.cat_flip_offset)
         validate_views(args)
@@ -250,7 +255,7 @@ def run_images(args, data_loader=None, model=None, n_synthetic_batches=4, stats=
         model, _ = models.model_factory(args)
         if args.resume:
             model, *_ = models.load_model(model, args.checkpoint_whole, optimizer=None, resume_optimizer=False,
-                                          drop_layers=False, load_amp=False)
+                                          drop_layers=False, load_amp=False, **({'use_ema': True} if getattr(args, 'use_ema', False) else {}))
     processors = [decoder.decoder_factory(args) for _ in range(IN_FLIGHT)]
     lanes = _lib.lane_streams(dev, IN_FLIGHT) if IN_FLIGHT > 1 else [torch.cuda.current_stream(dev)]
     if data_loader is None and getattr(args, 'raw_image_dir', None):

@@ -36,10 +36,13 @@ def basenet_factory(basenet_name):
 
 
 def load_model(model, ckpt_path, *, optimizer=None, drop_layers=True, drop_name='offset_convs',
-               resume_optimizer=True, optimizer2cuda=True, load_amp=False):
+               resume_optimizer=True, optimizer2cuda=True, load_amp=False, use_ema=False, ema=None):
     """Load `checkpoint['model_state_dict']` tolerant of a 'module.' prefix, missing / extra /
     shape-mismatched entries (reference networks.py:12-123).  Unlike the reference this never
-    blocks on input(): a missing file raises FileNotFoundError.
+    blocks on input(): a missing file raises FileNotFoundError.  use_ema: the weights are the averaged ones, the `module` entry of the
+    file's `ema_state_dict` (optim.ModelEma.state_dict(), written by save_model(ema_state=)), through the same merge; a file without
+    that entry raises KeyError.  ema: an optim.ModelEma bound to `model` that resumes from the file's `ema_state_dict` or, when the file
+    has none, starts again from the weights just loaded.
     Returns (model, optimizer, start_epoch, start_loss, amp_state_or_False)."""
     if not os.path.isfile(ckpt_path):
         raise FileNotFoundError(f'checkpoint {ckpt_path} does not exist')
@@ -48,7 +51,10 @@ def load_model(model, ckpt_path, *, optimizer=None, drop_layers=True, drop_name=
     amp_state = ckpt['amp'] if (load_amp and 'amp' in ckpt) else False
     own = model.state_dict()
     merged = OrderedDict()
-    for key, value in ckpt['model_state_dict'].items():
+    if use_ema and 'ema_state_dict' not in ckpt:
+        raise KeyError(f"checkpoint {ckpt_path} has no 'ema_state_dict': it was written without a weight average")
+    weights = ckpt['ema_state_dict']['module'] if use_ema else ckpt['model_state_dict']
+    for key, value in weights.items():
         if drop_layers and drop_name in key:
             continue
         if key.startswith('module') and not key.startswith('module_list'):
@@ -60,6 +66,11 @@ def load_model(model, ckpt_path, *, optimizer=None, drop_layers=True, drop_name=
     for key, value in own.items():
         merged.setdefault(key, value)
     model.load_state_dict(merged, strict=False)
+    if ema is not None:
+        if 'ema_state_dict' in ckpt:
+            ema.load_state_dict(ckpt['ema_state_dict'])
+        else:
+            ema.reset()
     if optimizer is not None and resume_optimizer and 'optimizer_state_dict' in ckpt:
         optimizer.load_state_dict(ckpt['optimizer_state_dict'])
         if torch.cuda.is_available() and optimizer2cuda:
@@ -70,14 +81,17 @@ def load_model(model, ckpt_path, *, optimizer=None, drop_layers=True, drop_name=
     return model, optimizer, start_epoch, start_loss, amp_state
 
 
-def save_model(path, epoch, train_loss, model, optimizer=None, amp_state=None):
-    """Checkpoint dict layout of the reference (networks.py:126-144)."""
+def save_model(path, epoch, train_loss, model, optimizer=None, amp_state=None, ema_state=None):
+    """Checkpoint dict layout of the reference (networks.py:126-144); ema_state (optim.ModelEma.state_dict()) goes beyond it, as
+    `ema_state_dict`."""
     net = model.module if hasattr(model, 'module') else model
     data = {'epoch': epoch, 'train_loss': train_loss, 'model_state_dict': net.state_dict()}
     if optimizer is not None:
         data['optimizer_state_dict'] = optimizer.state_dict()
     if amp_state is not None:
         data['amp'] = amp_state
+    if ema_state is not None:
+        data['ema_state_dict'] = ema_state
     torch.save(data, path)
 
 

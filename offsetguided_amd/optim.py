@@ -10,7 +10,12 @@ scaling, train_dist.py:336): the scale block also unscales, skips a step whose g
 The state keys are torch's (`step`, `exp_avg`, `exp_avg_sq`, `momentum_buffer`): a checkpoint written with torch.optim.Adam / SGD
 resumes here and the other way round.  `step` is counted on the host; the tensors under state[p]['step'] are brought up to date by
 state_dict().
+
+ModelEma keeps an exponential moving average of a model's weights in a shadow module; step(..., ema=ModelEma(model)) folds the
+average of every parameter it updates into the update launch itself (og_adam_step_ema_f32 / og_sgd_step_ema_f32) and averages the
+rest -- BatchNorm statistics, frozen parameters -- in one og_ema_lerp_f32 launch behind it.
 """
+import copy
 import math
 
 import numpy as np
@@ -122,6 +127,121 @@ def load_amp_state(scaler, state):
     return True
 
 
+class ModelEma:
+    """An exponential moving average of a model's weights (include/og_decoder.h, "weight average"): e' = e + (1 - decay) (x - e) per
+    element and update.  `module` is the shadow: a deep copy of the model (a DistributedDataParallel wrapper is unwrapped) in eval(),
+    without gradients, every tensor in the memory layout of its source -- hand it to InferenceEngine(...), engine.refresh(model=) or
+    save_model.  decay_at(t), t the updates taken so far: min(decay, (1 + t) / (10 + t)) with warmup (the TF / timm schedule), else
+    decay.  The shadow follows the tensors the model has when this is made (or bind() is called): move the model to its device and
+    memory format first.  optimizer.step(..., ema=this) is the fused update; update() averages every tensor in one launch of its own
+    (behind another optimizer).  There is no CPU path: on a CPU module everything but an update works."""
+
+    def __init__(self, model, decay=0.9998, warmup=True):
+        if not 0 <= decay < 1:
+            raise ValueError(f'ModelEma: decay must lie in [0, 1), got {decay}')
+        self.decay, self.warmup, self.updates = float(decay), bool(warmup), 0
+        model = _unwrap(model)
+        self.module = copy.deepcopy(model).eval().requires_grad_(False)
+        self._pool = _table.Pool()
+        self._signature = self._table = None
+        self._n_rows = self._n_chunks = self._prefix_at = 0
+        self.bind(model)
+
+    def bind(self, model):
+        """Pair the tensors of `model` (by state_dict() name) with the shadow's and bring every shadow tensor to its source's layout."""
+        source = _unwrap(model).state_dict(keep_vars=True)
+        shadow = self.module.state_dict(keep_vars=True)
+        if list(source) != list(shadow):
+            raise ValueError('ModelEma.bind: the model does not have the tensors of the shadow module')
+        with torch.no_grad():
+            for name, x in source.items():
+                e = shadow[name]
+                if e.shape != x.shape or e.dtype != x.dtype:
+                    raise ValueError(f'ModelEma.bind: {name} is {tuple(x.shape)} {x.dtype}, the shadow has {tuple(e.shape)} {e.dtype}')
+                if e.device != x.device or not _same_layout(e, x):
+                    e.data = torch.empty_like(x).copy_(e)
+        self.tensors = {name: (x, shadow[name]) for name, x in source.items()}      # name -> (source tensor, shadow tensor)
+        self._shadow_of = {x: e for x, e in self.tensors.values()}                   # tensors hash by identity
+        self._signature = None
+
+    @torch.no_grad()
+    def reset(self):
+        """Start the average again from the bound model's present weights (after they were loaded from a file without an average)."""
+        for x, e in self.tensors.values():
+            e.copy_(x)
+        self.updates = 0
+
+    def decay_at(self, t):
+        """The decay of the update after t updates (Python double)."""
+        return min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+
+    def shadow_of(self, tensor):
+        """The shadow tensor of a parameter or buffer of the bound model, or None."""
+        return self._shadow_of.get(tensor)
+
+    def state_dict(self):
+        return {'module': self.module.state_dict(), 'updates': self.updates}
+
+    def load_state_dict(self, state):
+        self.module.load_state_dict(state['module'])        # copies in place: the layouts stay
+        self.updates = int(state['updates'])
+
+    @torch.no_grad()
+    def update(self, skip=()):
+        """Queue one update of the average on the current stream, at decay_at(updates): ONE og_ema_lerp_f32 launch over every
+        floating tensor of the shadow's state_dict() whose source is not in `skip` (the parameters an optimizer's fused update has
+        just averaged), copy_ for the integer buffers (num_batches_tracked); updates += 1.  Never waits for the device."""
+        lib, dev = None, None
+        rows, counts, ints, seen = [], [], [], set()
+        for name, (x, e) in self.tensors.items():
+            if e in seen:             # one tensor under two names (tied weights) is averaged once
+                continue
+            seen.add(e)
+            if not x.is_cuda or not e.is_cuda:
+                raise _lib.OgError(f'ModelEma.update: {name} on {x.device}; the HIP kernels need GPU tensors (offsetguided_amd has no '
+                                   'CPU path)')
+            if not e.is_floating_point():
+                ints.append((e, x))
+                continue
+            if x in skip or x.numel() == 0:
+                continue
+            if dev is None:
+                lib, dev = _lib.load(), x.device
+                chunk = lib.og_optim_chunk_elems()
+            _check_shadow(name, x, e, dev)
+            rows.append((e.data_ptr(), x.data_ptr(), x.numel()))
+            counts.append(-(-x.numel() // chunk))
+        omd = 1.0 - self.decay_at(self.updates)
+        if rows:
+            with torch.cuda.device(dev):
+                if rows != self._signature:
+                    raw, prefix, self._prefix_at = _table.pack(np.array(rows, dtype=np.int64).reshape(-1, 3), counts)
+                    self._table = _table.upload(raw, dev, self._pool)
+                    self._n_rows, self._n_chunks = len(rows), int(prefix[-1])
+                    self._signature = rows
+                at = self._table.data_ptr()
+                _lib.check(lib.og_ema_lerp_f32(at, at + self._prefix_at, self._n_rows, self._n_chunks, omd, _lib.stream_ptr(dev)), lib)
+        for e, x in ints:
+            e.copy_(x)
+        self.updates += 1
+
+
+def _unwrap(model):
+    return model.module if isinstance(model, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)) else model
+
+
+def _check_shadow(name, x, e, dev):
+    """A source tensor and its average as the kernels take them: dense fp32 on `dev` in one element order.  The shadow is the
+    caller's: a layout that differs is an error, not something to fix behind their back."""
+    if x.dtype != torch.float32 or e.dtype != torch.float32:
+        raise _lib.OgError(f'ModelEma: {name}: fp32 tensors only (got {x.dtype}, shadow {e.dtype})')
+    if x.device != dev or e.device != dev:
+        raise _lib.OgError(f'ModelEma: {name} on {x.device}, its shadow on {e.device}, the step on {dev}; one device')
+    if not _same_layout(e, x) or not _dense(x):
+        raise _lib.OgError(f'ModelEma: {name}: the shadow tensor (shape {tuple(e.shape)}, strides {e.stride()}) does not have the layout '
+                           f'of its source (shape {tuple(x.shape)}, strides {x.stride()}), or the source is not dense')
+
+
 class _DeviceOptimizer(torch.optim.Optimizer):
     MOMENTS = ()      # state keys of the m and v columns of the table
 
@@ -200,7 +320,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
     def _key(self, p, group, state):
         raise NotImplementedError
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
+        """avg: None, or (address table, omd) of a step with a weight average."""
         raise NotImplementedError
 
     def _after(self, entries):
@@ -239,17 +360,28 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         out.sort(key=lambda e: e[:2])               # stable: list order inside a segment
         return out
 
-    def _upload(self, entries, dev, lib):
+    def _averages(self, entries, dev, ema):
+        """The address of every entry's average in the shadow of `ema`, 0 where the parameter is not in it."""
+        out = []
+        for _, _, p, _, _ in entries:
+            e = ema.shadow_of(p)
+            if e is not None:
+                _check_shadow(f'a parameter of shape {tuple(p.shape)}', p, e, dev)
+            out.append(0 if e is None else e.data_ptr())
+        return out
+
+    def _upload(self, entries, dev, lib, ema=None):
         chunk = lib.og_optim_chunk_elems()
         moments = self.MOMENTS + (None,) * (2 - len(self.MOMENTS))
         rows = [(p.data_ptr(), g.data_ptr(), *(st[k].data_ptr() if k and st.get(k) is not None else 0 for k in moments), p.numel())
                 for _, _, p, g, st in entries]
         keys = [e[:2] for e in entries]
-        signature = (rows, keys)
+        averages = None if ema is None else self._averages(entries, dev, ema)      # travels behind the rows, before the prefix
+        signature = (rows, keys) if ema is None else (rows, keys, averages)
         if signature == self._signature:
             return
         table = np.array(rows, dtype=np.int64).reshape(-1, 5)
-        raw, prefix, self._prefix_at = _table.pack(table, -(-table[:, 4] // chunk))
+        raw, prefix, self._prefix_at = _table.pack(table, -(-table[:, 4] // chunk), averages)
         self._segments = []
         for i, key in enumerate(keys):
             if i == 0 or key != keys[i - 1]:
@@ -260,11 +392,13 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         self._signature = signature
 
     @torch.no_grad()
-    def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8, scaler=None):
+    def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8, scaler=None, ema=None):
         """Queue one optimisation step on the current stream.  loss: the weighted fp32 loss on the device (a batch whose loss exceeds
         loss_limit is dropped); max_grad_norm: clip_grad_norm_'s max_norm over every gradient.  With neither, only the update runs.
         scaler: the DeviceLossScaler whose scale(loss) was sent backward -- the sum of squares always runs, the scale block unscales
         (and clips) with one number, skips the step on a non-finite gradient and moves the loss scale; loss is the unscaled one.
+        ema: a ModelEma -- the update launches average every parameter they step that is in its shadow (also on a dropped or skipped
+        step: the average follows the weights the model has), one more launch averages the shadow's other tensors, ema.updates += 1.
         Never waits for the device."""
         out = None
         if closure is not None:
@@ -279,12 +413,15 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         lib = _lib.load()
         entries = self._entries(dev)
         if not entries:
+            if ema is not None:
+                ema.update()
             return out
         with torch.cuda.device(dev):
             ws = self._workspace(dev, lib)
-            self._upload(entries, dev, lib)
+            self._upload(entries, dev, lib, ema)
             stream = _lib.stream_ptr(dev)
             rows, prefix = self._table.data_ptr(), self._table.data_ptr() + self._prefix_at
+            avg = None if ema is None else (rows + 40 * self._n_rows, 1.0 - ema.decay_at(ema.updates))
             state_ptr = None
             if loss is not None or math.isfinite(max_grad_norm) or scaler is not None:
                 if loss is not None:
@@ -303,7 +440,12 @@ class _DeviceOptimizer(torch.optim.Optimizer):
                                                          stream), lib)
                 state_ptr = _lib.ptr(ws)
             for gi, key, first, count in self._segments:
-                self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream)
+                if avg is None:
+                    self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream)
+                else:
+                    self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream, avg)
+            if ema is not None:
+                ema.update(skip={p for _, _, p, _, _ in entries if ema.shadow_of(p) is not None})
         self._after(entries)
         return out
 
@@ -328,9 +470,14 @@ class DeviceAdam(_DeviceOptimizer):
     def _key(self, p, group, state):
         return self._steps[p]
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
         t = key + 1
         b1, b2 = group['betas']
+        if avg is not None:
+            _lib.check(lib.og_adam_step_ema_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], b1, b2, 1.0 - b1,
+                                                1.0 - b2, group['eps'], group['weight_decay'], 1.0 - b1 ** t, 1.0 - b2 ** t,
+                                                int(group.get('adam_w_mode', True)), *avg, stream), lib)
+            return
         _lib.check(lib.og_adam_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], b1, b2, 1.0 - b1, 1.0 - b2,
                                         group['eps'], group['weight_decay'], 1.0 - b1 ** t, 1.0 - b2 ** t,
                                         int(group.get('adam_w_mode', True)), stream), lib)
@@ -362,7 +509,11 @@ class DeviceSGD(_DeviceOptimizer):
     def _key(self, p, group, state):
         return 1 if p in self._fresh else 0
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream):
+    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
+        if avg is not None:
+            _lib.check(lib.og_sgd_step_ema_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], group['momentum'],
+                                               group['weight_decay'], key, *avg, stream), lib)
+            return
         _lib.check(lib.og_sgd_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], group['momentum'],
                                        group['weight_decay'], key, stream), lib)
 

@@ -8,6 +8,8 @@
   apex SyncBatchNorm                      -> torch.nn.SyncBatchNorm (optional, --no-sync-bn)
   apex FusedAdam                          -> torch.optim.Adam(fused=True); --device-step: optim.DeviceAdam / DeviceSGD (csrc/optim.hip),
     loss.item() batch drop (:322)             gradient clipping and the batch drop as one device-side scale: no host wait in the step
+  (no weight average in the reference)    -> --ema-decay D: optim.ModelEma, averaged inside the --device-step update launch; the
+                                              checkpoint carries it (`ema_state_dict`), evaluate --use-ema scores it
   mask/gather losses                      -> fused HIP loss kernels (models/losses.py, csrc/losses.hip)
 
 One process per GPU (`python -m torch.distributed.run --nproc-per-node N -m offsetguided_amd.train_dist`);
@@ -25,7 +27,7 @@ import torch
 
 from . import _lib, encoder, models, optim, sharding, synth, transforms
 from .config import coco_data as cd
-from .utils import AverageMeter, adjust_learning_rate
+from .utils import AverageMeter, adjust_learning_rate, boolean_string
 
 
 def train_cli(argv=None):
@@ -88,6 +90,11 @@ def train_cli(argv=None):
                         'gradient clipping are one device-side scale, losses stay on the device between --print-freq lines')
     g.add_argument('--max-grad-norm', default=float('inf'), type=float,
                    help='clip the norm of all gradients to this value, as torch.nn.utils.clip_grad_norm_ does (with --device-step)')
+    g.add_argument('--ema-decay', default=None, type=float, metavar='D',
+                   help='keep an exponential moving average of the weights with decay D, 0 <= D < 1 (optim.ModelEma; with '
+                        '--device-step: the update launch averages what it steps); every checkpoint carries it as ema_state_dict')
+    g.add_argument('--ema-warmup', default=True, type=boolean_string,
+                   help='with --ema-decay: the decay of update t is min(D, (1 + t) / (10 + t))')
     g = p.add_argument_group('apex configuration (train_dist.py:77-82)')
     g.add_argument('--opt-level', type=str, default=None, choices=['O0', 'O1', 'O2', 'O3'],
                    help='O0: fp32, no autocast; O1: fp16 autocast with a device-side loss scaler (optim.DeviceLossScaler, needs '
@@ -117,6 +124,11 @@ def train_cli(argv=None):
         p.error('--max-grad-norm is applied by the device-side step: add --device-step')
     if not args.max_grad_norm > 0:
         p.error('--max-grad-norm must be positive')
+    if args.ema_decay is not None:
+        if not args.device_step:
+            p.error('--ema-decay is averaged by the device-side step: add --device-step')
+        if not 0 <= args.ema_decay < 1:
+            p.error('--ema-decay must lie in [0, 1)')
     if bool(args.train_annotations) != bool(args.train_image_dir):
         p.error('--train-annotations and --train-image-dir go together')
     if args.train_annotations:
@@ -269,7 +281,7 @@ def train_step(model, criterion, optimizer, images, annos, lambdas, autocast_dty
 
 
 def train_step_device(model, criterion, optimizer, images, annos, lambdas, autocast_dtype=torch.bfloat16, max_grad_norm=float('inf'),
-                      world=1, scaler=None):
+                      world=1, scaler=None, ema=None):
     """train_step for optim.DeviceAdam / DeviceSGD: nothing is read back.  backward() runs on the real loss; the step multiplies the
     gradients by the device-side scale -- 0 for a batch whose loss exceeds 1e8 (train_dist.py:322-325) or whose gradients are not
     finite, the clip_grad_norm_ coefficient of --max-grad-norm otherwise.  Under DDP the gradients are all-reduced when backward()
@@ -277,7 +289,7 @@ def train_step_device(model, criterion, optimizer, images, annos, lambdas, autoc
     batches.  scaler (optim.DeviceLossScaler, --opt-level O1): backward() runs on scaler.scale(loss); the step unscales, and a step
     whose gradients overflowed is skipped and moves the loss scale; the drop still looks at the unscaled loss.  Under DDP an inf or
     NaN in any rank's gradients is non-finite on every rank after the all-reduce, so every rank takes the same decision and keeps the
-    same loss scale without another collective.  Returns (loss, per-head losses) as device tensors."""
+    same loss scale without another collective.  ema (optim.ModelEma, --ema-decay): the step averages the weights it writes.  Returns (loss, per-head losses) as device tensors."""
     optimizer.zero_grad(set_to_none=True)
     dev_type = 'cuda' if images.is_cuda else 'cpu'
     with torch.autocast(dev_type, dtype=autocast_dtype, enabled=autocast_dtype is not None):
@@ -294,10 +306,11 @@ def train_step_device(model, criterion, optimizer, images, annos, lambdas, autoc
     if world > 1:
         guard = loss.clone()
         torch.distributed.all_reduce(guard, op=torch.distributed.ReduceOp.MAX)
+    extra = {} if ema is None else {'ema': ema}
     if scaler is None:
-        optimizer.step(loss=guard, max_grad_norm=max_grad_norm)
+        optimizer.step(loss=guard, max_grad_norm=max_grad_norm, **extra)
     else:
-        optimizer.step(loss=guard, max_grad_norm=max_grad_norm, scaler=scaler)
+        optimizer.step(loss=guard, max_grad_norm=max_grad_norm, scaler=scaler, **extra)
     return loss, [l.detach() if torch.is_tensor(l) else l for l in multi_losses]
 
 
@@ -322,24 +335,36 @@ def make_optimizer(args, model, world, use_cuda):
     return torch.optim.SGD(params, lr=lr, momentum=args.momentum, weight_decay=args.weight_decay)
 
 
-def load_checkpoint(args, model, optimizer, use_cuda, scaler=None):
+def make_ema(args, model):
+    """--ema-decay -> optim.ModelEma over the model as it stands (on its device, in its memory format), or None."""
+    decay = getattr(args, 'ema_decay', None)
+    return None if decay is None else optim.ModelEma(model, decay=decay, warmup=getattr(args, 'ema_warmup', True))
+
+
+def load_checkpoint(args, model, optimizer, use_cuda, scaler=None, ema=None):
     """--resume (train_dist.py:230-236, :267-268): weights, optimizer state unless --drop-optim-state, and the epoch the LR schedule
     is at unless --recount-epoch.  Without --resume, --checkpoint-whole initialises the weights only (fine-tuning, as
     evaluate.py:189-191 loads it); a path that does not exist is an error (load_model raises FileNotFoundError), never a silent
     random init.  scaler: resumed from the checkpoint's `amp` entry (train_dist.py:234-236) unless --drop-amp-state; a checkpoint
-    without one leaves it as made.  -> (model, optimizer, start_epoch, start_loss or None)."""
+    without one leaves it as made.  ema (optim.ModelEma bound to model): resumed from the checkpoint's `ema_state_dict`; a checkpoint
+    without one, --drop-optim-state and a --checkpoint-whole start begin the average at the loaded weights.  -> (model, optimizer, start_epoch, start_loss or None)."""
     drop_layers = getattr(args, 'drop_layers', False)
     if args.resume:
         if not args.checkpoint_whole:
             raise ValueError('--resume needs --checkpoint-whole <file>')
         model, optimizer, start_epoch, start_loss, amp_state = models.load_model(
             model, args.checkpoint_whole, optimizer=optimizer, resume_optimizer=getattr(args, 'resume_optimizer', True),
-            drop_layers=drop_layers, optimizer2cuda=use_cuda, load_amp=scaler is not None and getattr(args, 'load_amp', True))
+            drop_layers=drop_layers, optimizer2cuda=use_cuda, load_amp=scaler is not None and getattr(args, 'load_amp', True),
+            **({} if ema is None else {'ema': ema}))
         if scaler is not None:
             optim.load_amp_state(scaler, amp_state)
+        if ema is not None and not getattr(args, 'resume_optimizer', True):
+            ema.reset()
         return model, optimizer, 0 if getattr(args, 'recount_epoch', False) else start_epoch, start_loss
     if args.checkpoint_whole:
         model, *_ = models.load_model(model, args.checkpoint_whole, optimizer=None, resume_optimizer=False, drop_layers=drop_layers)
+        if ema is not None:
+            ema.reset()
     return model, optimizer, 0, None
 
 
@@ -358,12 +383,12 @@ def describe_losses(args):
     return ' + '.join(parts) + ' losses' + (', sqrt' if args.sqrt_re else '') + ('' if args.fused_losses else ', torch-formulated')
 
 
-def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment=None, rng=None, amp=None):
+def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment=None, rng=None, amp=None, ema=None):
     """BASELINE configs[4]: step time of the DDP training step (fused HIP losses, device-side GT encoding, bf16 autocast)
     and the gradient all-reduce's bus bandwidth.  The all-reduce overlaps backward inside the step, so its bandwidth is
     measured on its own: the same payload (one flat buffer of the gradients' size, the bucketed hook's dtype) reduced
     back to back over RCCL; bus GB/s = bytes x 2 (N - 1) / N / time (ring convention).  `exposed_comm_ms` = step time
-    minus the same step under no_sync().  amp: amp_setup's pair; None = bf16 autocast, no scaler."""
+    minus the same step under no_sync().  amp: amp_setup's pair; None = bf16 autocast, no scaler.  ema: make_ema's."""
     import contextlib
     import json
     use_cuda = dev.type == 'cuda'
@@ -383,7 +408,10 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
                     images, annos = pool[step % len(pool)]
                 if encoders is not None:
                     annos = encode_targets(encoders, *annos)
-                if device_step:
+                if ema is not None:
+                    train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype, args.max_grad_norm,
+                                      world, scaler, ema)
+                elif device_step:
                     train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype, args.max_grad_norm,
                                       world, scaler)
                 else:
@@ -408,6 +436,8 @@ def bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, wo
         extra['amp'] = 'fp16'
         extra['loss_scale'] = float(scaler.loss_scale)
         extra['overflow_steps'] = int(scaler.overflow_steps)
+    if ema is not None:
+        extra['ema'] = ema.decay
     if augment is not None:
         torch.cuda.synchronize(dev)               # the events are complete before they are read
         us =[a.elapsed_time(b) * 1e3 for a, b in augment_events]
@@ -473,7 +503,11 @@ def main(argv=None):
     autocast_dtype, scaler = amp_setup(args, dev, use_cuda)
     # continue a run (train_dist.py:219-233): weights, optimizer state and the epoch the LR schedule is at.  Before the DDP
     # wrap, so every rank loads the same state and the first broadcast has nothing to fix.
-    model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda, scaler)
+    ema = make_ema(args, model)
+    if ema is None:
+        model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda, scaler)
+    else:
+        model, optimizer, start_epoch, start_loss = load_checkpoint(args, model, optimizer, use_cuda, scaler, ema)
     if args.resume and rank == 0:
         print(f'resumed {args.checkpoint_whole}: next epoch {start_epoch}, last train loss {start_loss:.4f}')
     if world > 1:
@@ -519,7 +553,7 @@ def main(argv=None):
                                                  scale=args.include_scale)))
     if args.bench:
         return bench_steps(args, model, criterion, optimizer, pool, encoders, dev, rank, world, augment, aug_rng,
-                           None if args.opt_level is None else (autocast_dtype, scaler))
+                           None if args.opt_level is None else (autocast_dtype, scaler), **({} if ema is None else {'ema': ema}))
     batch_time = AverageMeter()   # over the whole run: the first steps (MIOpen find, allocator warm-up) do not bias an epoch
     # --epochs MORE epochs after a resume, as the reference counts them (train_dist.py:269)
     for epoch in range(start_epoch, start_epoch + args.epochs):
@@ -533,7 +567,10 @@ def main(argv=None):
                 images, annos = pool[step % len(pool)]
             if encoders is not None:
                 annos = encode_targets(encoders, *annos)
-            if args.device_step:
+            if ema is not None:
+                loss, _ = train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype,
+                                            args.max_grad_norm, world, scaler, ema)
+            elif args.device_step:
                 loss, _ = train_step_device(model, criterion, optimizer, images, annos, args.lambdas, autocast_dtype,
                                             args.max_grad_norm, world, scaler)
             else:
@@ -559,7 +596,8 @@ def main(argv=None):
                              if scaler is not None else ''))
         if rank == 0:
             models.save_model(os.path.join(args.checkpoint_path, f'PoseNet_{epoch}_epoch.pth'), epoch, losses.avg, model,
-                              optimizer, amp_state=optim.amp_state_dict(scaler) if scaler is not None else None)
+                              optimizer, amp_state=optim.amp_state_dict(scaler) if scaler is not None else None,
+                              **({} if ema is None else {'ema_state': ema.state_dict()}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
