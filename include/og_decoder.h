@@ -788,7 +788,8 @@ int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspa
  *       dynamic (dropped or not):  u = unskipped + 1;  if u == scale_window:  t = S * scale_factor;
  *                           S' = t > max_scale ? max_scale : t;  u = 0;  then unskipped' = u
  *   A static scaler (dynamic == 0) leaves S and unskipped alone.  With S a power of two every one of these operations is exact, so a
- *   step on S * g equals the step on g bit for bit; S == 1 static is og_step_scale_f32.  apex 0.1's LossScaler defaults: S = 2^16,
+ *   step on S * g equals the step on g bit for bit; S == 1 static is og_step_scale_f32 (ONE kernel: og_step_scale_f32 launches the
+ *   form in which S = 1, static, is a constant and no scaler word is read or written).  apex 0.1's LossScaler defaults: S = 2^16,
  *   scale_factor 2, scale_window 2000, min_scale 1, max_scale 2^24; this text is the specification (bit parity with apex: not pinned).
  *   OG_EINVAL besides og_step_scale_f32's: a null or misaligned scaler block, scale_factor <= 1, scale_window < 1, min_scale <= 0,
  *   max_scale < min_scale, a NaN or infinite one of them.  The block's contents are device memory and are not validated.
@@ -824,8 +825,9 @@ int og_coco_masks_u8(const OgCocoMaskDesc *desc, void *workspace, size_t workspa
  *   A row with ema[r] == 0 runs exactly the plain update and nothing else is read or written.  The average follows p' on EVERY step,
  *   a dropped or overflow step (scale == 0) included: such a step is still the zero-gradient update here (moments decay, weight decay
  *   acts), and the average tracks the weights the model actually has.  A non-finite p' poisons e: not guarded against.  omd == 0
- *   leaves e as it is; omd == 1 gives e + (p' - e), which need not be p'.  og_adam_step_f32 / og_sgd_step_f32 launch the same kernels'
- *   instantiation without the average.
+ *   leaves e as it is; omd == 1 gives e + (p' - e), which need not be p'.  The four update entry points launch ONE kernel, instantiated
+ *   on its rule (Adam; SGD with or without a buffer) and on the average: og_adam_step_f32 / og_sgd_step_f32 take the form that never
+ *   reads `ema`.
  * og_ema_lerp_f32: the same three lines with x for p', for the tensors no update touches in a step (BatchNorm running statistics,
  * frozen parameters, a parameter without a gradient).  Table: `rows` int64[n_rows][3], one row (e, x, numel) -- two device addresses
  * of dense fp32 data in one common element order, 4-byte aligned, any offset beyond that; e is read and written, x read -- and the

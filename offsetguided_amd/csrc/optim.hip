@@ -4,9 +4,13 @@
 // 16-byte loads and stores wherever a tensor's address allows them, a scalar head and tail where it does not.  The arithmetic is the
 // header's list of individually rounded fp32 operations (the library is built with -ffp-contract=off, correctly rounded divide and
 // sqrt): tests/optim_common.py restates it in numpy and the GPU tests compare bit for bit.  No float atomics anywhere: the sum of
-// squares goes through per-chunk partials in double and a fixed-order reduction.  The updates are templates on EMA: with it a row
-// that has an average (the `ema` address table) folds e' = e + omd * (p' - e) into the store of p', 8 B per parameter more and no
-// second pass over p; og_ema_lerp_f32 is the same rule over the tensors no update touches.
+// squares goes through per-chunk partials in double and a fixed-order reduction.  There is ONE update kernel, update_kernel<Rule,
+// EMA>: the rule (AdamRule, SgdRule<HAS_BUF>) says which moment columns exist and holds the per-element arithmetic, the kernel
+// walks, loads and stores.  With EMA a row that has an average (the `ema` address table) folds e' = e + omd * (p' - e) into the
+// store of p', 8 B per parameter more and no second pass over p.  ema_lerp_kernel, the same three lines over the tensors no update
+// touches, is a kernel of its own on the shared helpers: its rows are (e, x, numel) and its frame is e's, which as a rule would put
+// a row-layout branch into every update.  There is ONE scale block, step_scale_kernel<AMP>: the plain form is the scaler form with
+// S = 1, static, and touches no scaler word.
 #include "table.h"
 
 namespace {
@@ -52,7 +56,8 @@ __device__ __forceinline__ bool locate(const int64_t *rows, const int32_t *prefi
     return span_of(prefix, r, chunk, row.n, s);
 }
 
-// The vector frame of a span (table.h) is anchored on `anchor` (p for the updates, g for the sum of squares), given at element lo.
+// The vector frame of a span (table.h) is anchored on `anchor` (p for the updates, g for the sum of squares, e for the lerp), given
+// at element lo.
 __device__ __forceinline__ void frame(const gfloat *anchor, Span &s)
 {
     s.f = og_frame(anchor, (int)(s.hi - s.lo), 4);
@@ -151,22 +156,6 @@ __device__ __forceinline__ float clip_coefficient(float norm, float max_norm)
     return c < 1.f ? c : 1.f;
 }
 
-__global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double *__restrict__ partials, int n_partials,
-                                                                   const float *__restrict__ loss, float loss_limit, float max_norm,
-                                                                   float *__restrict__ state)
-{
-    double n2;
-    if (!sum_partials(partials, n_partials, n2)) return;
-    const float norm = (float)sqrt(n2);
-    const bool drop = (loss != nullptr && *loss > loss_limit) || !isfinite(n2);
-    const float scale = drop ? 0.f : clip_coefficient(norm, max_norm);
-    state[0] = scale;
-    state[1] = norm;
-    if (drop) reinterpret_cast<int *>(state)[2] += 1;
-}
-
-// The same block behind a loss scaler (header: og_step_scale_amp_f32): the gradients carry the factor S = scaler[0]; the scale it
-// writes unscales and clips in one number, an overflow skips the step and moves S.  Plain loads and stores by thread 0.
 struct AmpArgs {
     int dynamic;
     float factor;
@@ -174,41 +163,45 @@ struct AmpArgs {
     float min_scale, max_scale;
 };
 
-__global__ __launch_bounds__(SCALE_THREADS) void step_scale_amp_kernel(const double *__restrict__ partials, int n_partials,
-                                                                       const float *__restrict__ loss, float loss_limit, float max_norm,
-                                                                       float *__restrict__ state, float *__restrict__ scaler, AmpArgs a)
+// Thread 0 turns the sum of squares into the state block the updates read.  AMP (header: og_step_scale_amp_f32): the gradients
+// carry the factor S = scaler[0]; the scale unscales and clips in one number, an overflow skips the step and moves S.  Without AMP
+// (og_step_scale_f32) S = 1, static: the same lines, `scaler` is never touched and `a` is never read.  Plain loads and stores.
+template <bool AMP>
+__global__ __launch_bounds__(SCALE_THREADS) void step_scale_kernel(const double *__restrict__ partials, int n_partials,
+                                                                   const float *__restrict__ loss, float loss_limit, float max_norm,
+                                                                   float *__restrict__ state, float *__restrict__ scaler, AmpArgs a)
 {
     double n2;
     if (!sum_partials(partials, n_partials, n2)) return;
-    int *dropped = reinterpret_cast<int *>(state) + 2;
     int *words = reinterpret_cast<int *>(scaler);          // [1] unskipped, [2] overflows, [3] last_overflow
-    const float S = scaler[0];
+    const float S = AMP ? scaler[0] : 1.f;
+    const bool dynamic = AMP && a.dynamic;
     const bool overflow = !isfinite(n2);
     const double root = sqrt(n2);
     const double unscaled = root / (double)S;
     const float norm = (float)unscaled;
-    float scale = 0.f, next = S;
-    int u = words[1];
-    if (overflow) {
-        words[3] = 1;
-        if (a.dynamic) {
+    // a dynamic scaler answers for an overflow itself (a skipped step, not an exploding batch); everything else that zeroes the
+    // scale is ONE dropped step
+    const bool drop = overflow ? !dynamic : (loss != nullptr && *loss > loss_limit);
+    float scale = 0.f;
+    if (!overflow && !drop) {
+        const float inv = 1.f / S;
+        const float c = clip_coefficient(norm, max_norm);
+        scale = c * inv;
+    }
+    state[0] = scale;
+    state[1] = norm;
+    if (drop) reinterpret_cast<int *>(state)[2] += 1;
+    if (AMP) words[3] = overflow;
+    if (dynamic) {
+        float next = S;
+        int u = words[1];
+        if (overflow) {
             const float t = S / a.factor;
             next = t < a.min_scale ? a.min_scale : t;
             u = 0;
             words[2] += 1;
         } else {
-            *dropped += 1;
-        }
-    } else {
-        words[3] = 0;
-        if (loss != nullptr && *loss > loss_limit) {
-            *dropped += 1;
-        } else {
-            const float inv = 1.f / S;
-            const float c = clip_coefficient(norm, max_norm);
-            scale = c * inv;
-        }
-        if (a.dynamic) {
             u = u + 1;
             if (u == a.window) {
                 const float t = S * a.factor;
@@ -216,47 +209,85 @@ __global__ __launch_bounds__(SCALE_THREADS) void step_scale_amp_kernel(const dou
                 u = 0;
             }
         }
-    }
-    state[0] = scale;
-    state[1] = norm;
-    if (a.dynamic) {
         scaler[0] = next;
         words[1] = u;
     }
 }
 
 // ---- updates -------------------------------------------------------------------------------------------------------------------
+// A rule: HAS_M / HAS_V (which moment columns of the row exist: they are written when they do), reads_m() (m is also read) and
+// element(), the header's list for ONE element, every line one individually rounded fp32 operation.
 struct AdamArgs {
     float lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2;
     int adam_w_mode;
 };
 
-__device__ __forceinline__ void adam_element(const AdamArgs &a, float scale, float &p, float g, float &m, float &v)
-{
-    float ge = (scale == 0.f) ? 0.f : g * scale;
-    if (a.wd != 0.f && !a.adam_w_mode) {
-        const float t = a.wd * p;
-        ge = ge + t;
+struct AdamRule {
+    static constexpr bool HAS_M = true, HAS_V = true;
+    AdamArgs a;
+
+    __device__ __forceinline__ bool reads_m() const { return true; }
+
+    __device__ __forceinline__ void element(float scale, float &p, float g, float &m, float &v) const
+    {
+        float ge = (scale == 0.f) ? 0.f : g * scale;
+        if (a.wd != 0.f && !a.adam_w_mode) {
+            const float t = a.wd * p;
+            ge = ge + t;
+        }
+        const float x = a.b1 * m;
+        const float y = a.omb1 * ge;
+        m = x + y;
+        const float c = a.b2 * v;
+        const float d = a.omb2 * ge;
+        const float e = d * ge;
+        v = c + e;
+        const float mh = m / a.bc1;
+        const float q = v / a.bc2;
+        const float r = sqrtf(q);
+        const float den = r + a.eps;
+        float u = mh / den;
+        if (a.wd != 0.f && a.adam_w_mode) {
+            const float t = a.wd * p;
+            u = u + t;
+        }
+        const float s = a.lr * u;
+        p = p - s;
     }
-    const float x = a.b1 * m;
-    const float y = a.omb1 * ge;
-    m = x + y;
-    const float c = a.b2 * v;
-    const float d = a.omb2 * ge;
-    const float e = d * ge;
-    v = c + e;
-    const float mh = m / a.bc1;
-    const float q = v / a.bc2;
-    const float r = sqrtf(q);
-    const float den = r + a.eps;
-    float u = mh / den;
-    if (a.wd != 0.f && a.adam_w_mode) {
-        const float t = a.wd * p;
-        u = u + t;
+};
+
+struct SgdArgs {
+    float lr, mom, wd;
+    int first;
+};
+
+// m is the momentum buffer: read only when HAS_BUF && !first, written only when HAS_BUF
+template <bool HAS_BUF>
+struct SgdRule {
+    static constexpr bool HAS_M = HAS_BUF, HAS_V = false;
+    SgdArgs a;
+
+    __device__ __forceinline__ bool reads_m() const { return HAS_BUF && !a.first; }
+
+    __device__ __forceinline__ void element(float scale, float &p, float g, float &m, float &) const
+    {
+        float ge = (scale == 0.f) ? 0.f : g * scale;
+        if (a.wd != 0.f) {
+            const float t = a.wd * p;
+            ge = ge + t;
+        }
+        float step = ge;
+        if (HAS_BUF) {
+            if (!a.first) {
+                const float t = a.mom * m;
+                step = t + ge;
+            }
+            m = step;
+        }
+        const float s = a.lr * step;
+        p = p - s;
     }
-    const float s = a.lr * u;
-    p = p - s;
-}
+};
 
 // The average behind an update (header: "weight average"): x is p' as it is stored, three individually rounded operations.
 __device__ __forceinline__ float ema_element(float omd, float x, float e)
@@ -268,143 +299,57 @@ __device__ __forceinline__ float ema_element(float omd, float x, float e)
 
 __device__ __forceinline__ void ema4(float omd, const f4 &x, f4 &e)
 {
-    e.x = ema_element(omd, x.x, e.x);
-    e.y = ema_element(omd, x.y, e.y);
-    e.z = ema_element(omd, x.z, e.z);
-    e.w = ema_element(omd, x.w, e.w);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] = ema_element(omd, x[c], e[c]);
 }
 
-// The row's average, or null: without EMA the table is never read
-template <bool EMA>
-__device__ __forceinline__ gfloat *average_of(const int64_t *ema, const Row &row)
-{
-    return EMA ? (gfloat *)(uintptr_t)ema[row.index] : nullptr;
-}
-
-template <bool EMA>
-__global__ __launch_bounds__(OPTIM_THREADS) void adam_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
-                                                                  int n_rows, int chunk_first, const float *__restrict__ state, AdamArgs a,
-                                                                  const int64_t *__restrict__ ema, float omd)
+// The frame is p's; g, the moments and the average take 16-byte accesses on their own alignment.  A row whose `ema` address is 0
+// is stepped without an average; without EMA the `ema` table is never read.
+template <class Rule, bool EMA>
+__global__ __launch_bounds__(OPTIM_THREADS) void update_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
+                                                               int n_rows, int chunk_first, const float *__restrict__ state, Rule rule,
+                                                               const int64_t *__restrict__ ema, float omd)
 {
     Row row;
     Span s;
     if (!locate(rows, prefix, n_rows, chunk_first + blockIdx.x, row, s)) return;
     const float scale = state ? state[0] : 1.f;
     frame(row.p + s.lo, s);
-    const bool gv = aligned16(row.g + s.vs), mv = aligned16(row.m + s.vs), vv = aligned16(row.v + s.vs);
-    gfloat *const avg = average_of<EMA>(ema, row);
+    const bool gv = aligned16(row.g + s.vs), mv = Rule::HAS_M && aligned16(row.m + s.vs), vv = Rule::HAS_V && aligned16(row.v + s.vs);
+    const bool read_m = rule.reads_m();
+    gfloat *const avg = EMA ? (gfloat *)(uintptr_t)ema[row.index] : nullptr;
     const bool has_avg = EMA && avg != nullptr, ev = has_avg && aligned16(avg + s.vs);
 #pragma unroll 2
     for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
         const long i = s.vs + 4L * k;
         f4 p = *(const gf4 *)(row.p + i);
         const f4 g = load4(row.g + i, gv);
-        f4 m = load4(row.m + i, mv);
-        f4 v = load4(row.v + i, vv);
-        f4 e = {0.f, 0.f, 0.f, 0.f};
+        f4 m = {0.f, 0.f, 0.f, 0.f}, v = m, e = m;
+        if (read_m) m = load4(row.m + i, mv);
+        if (Rule::HAS_V) v = load4(row.v + i, vv);
         if (has_avg) e = load4(avg + i, ev);
-#define ADAM_LANE(c)                                  \
-    {                                                 \
-        float p_ = p.c, m_ = m.c, v_ = v.c;           \
-        adam_element(a, scale, p_, g.c, m_, v_);      \
-        p.c = p_, m.c = m_, v.c = v_;                 \
-    }
-        ADAM_LANE(x) ADAM_LANE(y) ADAM_LANE(z) ADAM_LANE(w)
-#undef ADAM_LANE
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float p_ = p[c], m_ = m[c], v_ = v[c];
+            rule.element(scale, p_, g[c], m_, v_);
+            p[c] = p_, m[c] = m_, v[c] = v_;
+        }
         *(gf4 *)(row.p + i) = p;
-        store4(row.m + i, mv, m);
-        store4(row.v + i, vv, v);
+        if (Rule::HAS_M) store4(row.m + i, mv, m);
+        if (Rule::HAS_V) store4(row.v + i, vv, v);
         if (has_avg) {
             ema4(omd, p, e);
             store4(avg + i, ev, e);
         }
     }
-    const long e = edge_element(s);
-    if (e >= 0) {
-        float p = row.p[e], m = row.m[e], v = row.v[e];
-        adam_element(a, scale, p, row.g[e], m, v);
-        row.p[e] = p;
-        row.m[e] = m;
-        row.v[e] = v;
-        if (has_avg) {
-            avg[e] = ema_element(omd, p, avg[e]);
-        }
-    }
-}
-
-struct SgdArgs {
-    float lr, mom, wd;
-    int first;
-};
-
-// buf is read only when HAS_BUF && !first, written only when HAS_BUF
-template <bool HAS_BUF>
-__device__ __forceinline__ void sgd_element(const SgdArgs &a, float scale, float &p, float g, float &buf)
-{
-    float ge = (scale == 0.f) ? 0.f : g * scale;
-    if (a.wd != 0.f) {
-        const float t = a.wd * p;
-        ge = ge + t;
-    }
-    float step = ge;
-    if (HAS_BUF) {
-        if (!a.first) {
-            const float t = a.mom * buf;
-            step = t + ge;
-        }
-        buf = step;
-    }
-    const float s = a.lr * step;
-    p = p - s;
-}
-
-template <bool HAS_BUF, bool EMA>
-__global__ __launch_bounds__(OPTIM_THREADS) void sgd_step_kernel(const int64_t *__restrict__ rows, const int32_t *__restrict__ prefix,
-                                                                 int n_rows, int chunk_first, const float *__restrict__ state, SgdArgs a,
-                                                                 const int64_t *__restrict__ ema, float omd)
-{
-    Row row;
-    Span s;
-    if (!locate(rows, prefix, n_rows, chunk_first + blockIdx.x, row, s)) return;
-    const float scale = state ? state[0] : 1.f;
-    frame(row.p + s.lo, s);
-    const bool gv = aligned16(row.g + s.vs), mv = HAS_BUF && aligned16(row.m + s.vs);
-    const bool read_buf = HAS_BUF && !a.first;
-    gfloat *const avg = average_of<EMA>(ema, row);
-    const bool has_avg = EMA && avg != nullptr, ev = has_avg && aligned16(avg + s.vs);
-#pragma unroll 2
-    for (int k = threadIdx.x; k < s.f.n_vec; k += OPTIM_THREADS) {
-        const long i = s.vs + 4L * k;
-        f4 p = *(const gf4 *)(row.p + i);
-        const f4 g = load4(row.g + i, gv);
-        f4 m = {0.f, 0.f, 0.f, 0.f};
-        if (read_buf) m = load4(row.m + i, mv);
-        f4 e = {0.f, 0.f, 0.f, 0.f};
-        if (has_avg) e = load4(avg + i, ev);
-#define SGD_LANE(c)                                       \
-    {                                                     \
-        float p_ = p.c, m_ = m.c;                         \
-        sgd_element<HAS_BUF>(a, scale, p_, g.c, m_);      \
-        p.c = p_, m.c = m_;                               \
-    }
-        SGD_LANE(x) SGD_LANE(y) SGD_LANE(z) SGD_LANE(w)
-#undef SGD_LANE
-        *(gf4 *)(row.p + i) = p;
-        if (HAS_BUF) store4(row.m + i, mv, m);
-        if (has_avg) {
-            ema4(omd, p, e);
-            store4(avg + i, ev, e);
-        }
-    }
-    const long e = edge_element(s);
-    if (e >= 0) {
-        float p = row.p[e], m = read_buf ? row.m[e] : 0.f;
-        sgd_element<HAS_BUF>(a, scale, p, row.g[e], m);
-        row.p[e] = p;
-        if (HAS_BUF) row.m[e] = m;
-        if (has_avg) {
-            avg[e] = ema_element(omd, p, avg[e]);
-        }
+    const long j = edge_element(s);
+    if (j >= 0) {
+        float p = row.p[j], m = read_m ? row.m[j] : 0.f, v = Rule::HAS_V ? row.v[j] : 0.f;
+        rule.element(scale, p, row.g[j], m, v);
+        row.p[j] = p;
+        if (Rule::HAS_M) row.m[j] = m;
+        if (Rule::HAS_V) row.v[j] = v;
+        if (has_avg) avg[j] = ema_element(omd, p, avg[j]);
     }
 }
 
@@ -444,16 +389,65 @@ OG_API size_t og_optim_workspace_bytes(int n_chunks)
     return n_chunks < 0 ? 0 : (size_t)OPTIM_STATE_BYTES + (size_t)n_chunks * sizeof(double);
 }
 
+// ---- what the entry points share -------------------------------------------------------------------------------------------------
+// The workspace of n_chunks chunks and its two parts
+static int split_workspace(const char *name, int n_chunks, void *workspace, size_t workspace_bytes, float *&state, double *&partials)
+{
+    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
+    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
+               workspace_bytes, og_optim_workspace_bytes(n_chunks));
+    state = static_cast<float *>(workspace);
+    partials = reinterpret_cast<double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
+    return OG_OK;
+}
+
+static int check_scale(const char *name, int n_chunks, const float *loss, float loss_limit, float max_norm, void *workspace,
+                       size_t workspace_bytes, float *&state, double *&partials)
+{
+    OG_REQUIRE(n_chunks >= 0, OG_EINVAL, "%s: negative chunk count", name);
+    if (int rc = split_workspace(name, n_chunks, workspace, workspace_bytes, state, partials)) return rc;
+    OG_REQUIRE(!(max_norm != max_norm) && !(loss_limit != loss_limit), OG_EINVAL, "%s: NaN max_norm or loss_limit", name);
+    OG_REQUIRE(((uintptr_t)loss & 3u) == 0, OG_EINVAL, "%s: misaligned loss", name);
+    return OG_OK;
+}
+
+// with_ema: the _ema form of an update's entry point, which alone looks at `ema` and `omd`
+static int check_update(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
+                        int n_chunks, const void *state, const int64_t *ema, float omd)
+{
+    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
+    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
+    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
+    if (with_ema) {
+        OG_REQUIRE(ema && ((uintptr_t)ema & 7u) == 0, OG_EINVAL, "%s: null or misaligned ema table", name);
+        OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
+    }
+    return OG_OK;
+}
+
+// Behind check_update: with_ema == false launches the instantiation that never reads `ema`.
+template <class Rule>
+static int launch_update(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
+                         int n_chunks, const void *state, const Rule &rule, const int64_t *ema, float omd, void *stream)
+{
+    if (n_chunks == 0) return OG_OK;
+    const auto kernel = with_ema ? update_kernel<Rule, true> : update_kernel<Rule, false>;
+    hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows, chunk_first,
+                       static_cast<const float *>(state), rule, ema, omd);
+    OG_LAUNCH_CHECK(name);
+    return OG_OK;
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------------
 OG_API int og_grad_sumsq_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int n_chunks, void *workspace,
                              size_t workspace_bytes, void *stream)
 {
     const char *name = "og_grad_sumsq_f32";
+    float *state;
+    double *partials;
     if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
-    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
-    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
-               workspace_bytes, og_optim_workspace_bytes(n_chunks));
+    if (int rc = split_workspace(name, n_chunks, workspace, workspace_bytes, state, partials)) return rc;
     if (n_chunks == 0) return OG_OK;
-    double *partials = reinterpret_cast<double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
                        partials);
     OG_LAUNCH_CHECK(name);
@@ -464,16 +458,11 @@ OG_API int og_step_scale_f32(int n_chunks, const float *loss, float loss_limit, 
                              void *stream)
 {
     const char *name = "og_step_scale_f32";
-    OG_REQUIRE(n_chunks >= 0, OG_EINVAL, "%s: negative chunk count", name);
-    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
-    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
-               workspace_bytes, og_optim_workspace_bytes(n_chunks));
-    OG_REQUIRE(!(max_norm != max_norm) && !(loss_limit != loss_limit), OG_EINVAL, "%s: NaN max_norm or loss_limit", name);
-    OG_REQUIRE(((uintptr_t)loss & 3u) == 0, OG_EINVAL, "%s: misaligned loss", name);
-    float *state = static_cast<float *>(workspace);
-    const double *partials = reinterpret_cast<const double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
-    hipLaunchKernelGGL(step_scale_kernel, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss, loss_limit,
-                       max_norm, state);
+    float *state;
+    double *partials;
+    if (int rc = check_scale(name, n_chunks, loss, loss_limit, max_norm, workspace, workspace_bytes, state, partials)) return rc;
+    hipLaunchKernelGGL(step_scale_kernel<false>, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss,
+                       loss_limit, max_norm, state, static_cast<float *>(nullptr), AmpArgs{});
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }
@@ -483,12 +472,9 @@ OG_API int og_step_scale_amp_f32(int n_chunks, const float *loss, float loss_lim
                                  size_t workspace_bytes, void *stream)
 {
     const char *name = "og_step_scale_amp_f32";
-    OG_REQUIRE(n_chunks >= 0, OG_EINVAL, "%s: negative chunk count", name);
-    OG_REQUIRE(workspace && ((uintptr_t)workspace & 7u) == 0, OG_EINVAL, "%s: null or misaligned workspace", name);
-    OG_REQUIRE(workspace_bytes >= og_optim_workspace_bytes(n_chunks), OG_ENOSPC, "%s: workspace of %zu bytes, %zu needed", name,
-               workspace_bytes, og_optim_workspace_bytes(n_chunks));
-    OG_REQUIRE(!(max_norm != max_norm) && !(loss_limit != loss_limit), OG_EINVAL, "%s: NaN max_norm or loss_limit", name);
-    OG_REQUIRE(((uintptr_t)loss & 3u) == 0, OG_EINVAL, "%s: misaligned loss", name);
+    float *state;
+    double *partials;
+    if (int rc = check_scale(name, n_chunks, loss, loss_limit, max_norm, workspace, workspace_bytes, state, partials)) return rc;
     OG_REQUIRE(scaler && ((uintptr_t)scaler & 15u) == 0, OG_EINVAL, "%s: null or misaligned scaler block", name);
     // written so that a NaN fails each of them
     OG_REQUIRE(scale_factor > 1.f && scale_factor <= 3.4028234664e38f, OG_EINVAL, "%s: scale_factor must be a finite number above 1 (got %g)",
@@ -497,36 +483,19 @@ OG_API int og_step_scale_amp_f32(int n_chunks, const float *loss, float loss_lim
     OG_REQUIRE(min_scale > 0.f, OG_EINVAL, "%s: min_scale must be positive (got %g)", name, min_scale);
     OG_REQUIRE(max_scale >= min_scale && max_scale <= 3.4028234664e38f, OG_EINVAL, "%s: max_scale must be finite and not below min_scale (got %g, %g)",
                name, max_scale, min_scale);
-    float *state = static_cast<float *>(workspace);
-    const double *partials = reinterpret_cast<const double *>(static_cast<char *>(workspace) + OPTIM_STATE_BYTES);
     const AmpArgs a{dynamic != 0, scale_factor, scale_window, min_scale, max_scale};
-    hipLaunchKernelGGL(step_scale_amp_kernel, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss, loss_limit,
-                       max_norm, state, static_cast<float *>(scaler), a);
+    hipLaunchKernelGGL(step_scale_kernel<true>, dim3(1), dim3(SCALE_THREADS), 0, (hipStream_t)stream, partials, n_chunks, loss,
+                       loss_limit, max_norm, state, static_cast<float *>(scaler), a);
     OG_LAUNCH_CHECK(name);
     return OG_OK;
 }
 
-// Both forms of an update's entry point: ema == nullptr launches the instantiation without the average.
 static int adam_step(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
                      int n_chunks, const void *state, const AdamArgs &a, const int64_t *ema, float omd, void *stream)
 {
-    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
-    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
-    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
+    if (int rc = check_update(name, with_ema, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, ema, omd)) return rc;
     OG_REQUIRE(a.bc1 > 0.f && a.bc2 > 0.f, OG_EINVAL, "%s: bias corrections must be positive (bc1 %g, bc2 %g)", name, a.bc1, a.bc2);
-    if (with_ema) {
-        OG_REQUIRE(ema && ((uintptr_t)ema & 7u) == 0, OG_EINVAL, "%s: null or misaligned ema table", name);
-        OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
-    }
-    if (n_chunks == 0) return OG_OK;
-    if (with_ema)
-        hipLaunchKernelGGL(adam_step_kernel<true>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
-                           chunk_first, static_cast<const float *>(state), a, ema, omd);
-    else
-        hipLaunchKernelGGL(adam_step_kernel<false>, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix, n_rows,
-                           chunk_first, static_cast<const float *>(state), a, ema, omd);
-    OG_LAUNCH_CHECK(name);
-    return OG_OK;
+    return launch_update(name, with_ema, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, AdamRule{a}, ema, omd, stream);
 }
 
 OG_API int og_adam_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks,
@@ -545,33 +514,14 @@ OG_API int og_adam_step_ema_f32(const int64_t *rows, const int32_t *chunk_prefix
     return adam_step("og_adam_step_ema_f32", true, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
 }
 
-template <bool EMA>
-static void sgd_launch(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,
-                       const SgdArgs &a, const int64_t *ema, float omd, void *stream)
-{
-    if (a.mom != 0.f)
-        hipLaunchKernelGGL((sgd_step_kernel<true, EMA>), dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix,
-                           n_rows, chunk_first, static_cast<const float *>(state), a, ema, omd);
-    else
-        hipLaunchKernelGGL((sgd_step_kernel<false, EMA>), dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, rows, chunk_prefix,
-                           n_rows, chunk_first, static_cast<const float *>(state), a, ema, omd);
-}
-
+// mom == 0: the rule without a buffer
 static int sgd_step(const char *name, bool with_ema, const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first,
                     int n_chunks, const void *state, const SgdArgs &a, const int64_t *ema, float omd, void *stream)
 {
-    if (int rc = og_check_table(name, rows, chunk_prefix, n_rows, n_chunks)) return rc;
-    OG_REQUIRE(chunk_first >= 0, OG_EINVAL, "%s: negative first chunk %d", name, chunk_first);
-    OG_REQUIRE(((uintptr_t)state & 3u) == 0, OG_EINVAL, "%s: misaligned state block", name);
-    if (with_ema) {
-        OG_REQUIRE(ema && ((uintptr_t)ema & 7u) == 0, OG_EINVAL, "%s: null or misaligned ema table", name);
-        OG_REQUIRE(omd >= 0.f && omd <= 1.f, OG_EINVAL, "%s: omd = 1 - decay must lie in [0, 1] (got %g)", name, omd);      // a NaN fails it
-    }
-    if (n_chunks == 0) return OG_OK;
-    if (with_ema) sgd_launch<true>(rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
-    else sgd_launch<false>(rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, a, ema, omd, stream);
-    OG_LAUNCH_CHECK(name);
-    return OG_OK;
+    if (int rc = check_update(name, with_ema, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, ema, omd)) return rc;
+    if (a.mom != 0.f)
+        return launch_update(name, with_ema, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, SgdRule<true>{a}, ema, omd, stream);
+    return launch_update(name, with_ema, rows, chunk_prefix, n_rows, chunk_first, n_chunks, state, SgdRule<false>{a}, ema, omd, stream);
 }
 
 OG_API int og_sgd_step_f32(const int64_t *rows, const int32_t *chunk_prefix, int n_rows, int chunk_first, int n_chunks, const void *state,

@@ -5,7 +5,8 @@ step(loss=..., max_grad_norm=...) queues three launches on the current stream: t
 (the clip coefficient of torch.nn.utils.clip_grad_norm_ and the reference's `loss > 1e8` batch drop in ONE device-side number), and
 the update, which multiplies every gradient by that number.  Nothing is read back: `last_grad_norm` and `dropped_steps` are device
 tensors the caller converts when it prints.  step(..., scaler=DeviceLossScaler()) is the fp16 form (apex amp O1's dynamic loss
-scaling, train_dist.py:336): the scale block also unscales, skips a step whose gradients overflowed and moves the loss scale.
+scaling, train_dist.py:336): the scale block in its scaler form also unscales, skips a step whose gradients overflowed and moves the
+loss scale.  The update is one kernel with a rule: a subclass names its entry point and the rule's arguments (_rule), step() launches.
 
 The state keys are torch's (`step`, `exp_avg`, `exp_avg_sq`, `momentum_buffer`): a checkpoint written with torch.optim.Adam / SGD
 resumes here and the other way round.  `step` is counted on the host; the tensors under state[p]['step'] are brought up to date by
@@ -41,6 +42,39 @@ def _dense(t):
     return True
 
 
+def _no_cpu_path(owner, what, tensor):
+    """The error for a tensor that is not on a GPU; the caller tests is_cuda (in a step's loops, once per tensor) and raises it."""
+    return _lib.OgError(f'{owner}: {what} on {tensor.device}; the HIP kernels need GPU tensors (offsetguided_amd has no CPU path)')
+
+
+class _DeviceTable:
+    """A tensor table (_table.py) on the device, cached: put() packs and uploads only when what it was built from has changed."""
+
+    def __init__(self):
+        self._pool = _table.Pool()
+        self._signature = self._tensor = None
+        self.n_rows = self.n_chunks = self._extra_at = self._prefix_at = 0
+
+    def forget(self):
+        self._signature = None
+
+    def put(self, signature, rows, words, chunk, dev, extra=None):
+        """rows: a tuple of `words` int64 per tensor, the last its element count (`chunk` elements to a workgroup); extra: _table.pack's.
+        -> the host prefix of a table that was built anew, None when `signature` is the one the device table already has."""
+        if signature == self._signature:
+            return None
+        table = np.array(rows, dtype=np.int64).reshape(-1, words)
+        raw, prefix, self._prefix_at = _table.pack(table, -(-table[:, -1] // chunk), extra)
+        self._tensor = _table.upload(raw, dev, self._pool)
+        self.n_rows, self.n_chunks, self._extra_at = len(rows), int(prefix[-1]), 8 * table.size
+        self._signature = signature
+        return prefix
+
+    rows = property(lambda self: self._tensor.data_ptr())                        # device addresses of the table's three parts
+    extra = property(lambda self: self._tensor.data_ptr() + self._extra_at)
+    prefix = property(lambda self: self._tensor.data_ptr() + self._prefix_at)
+
+
 class DeviceLossScaler:
     """apex amp O1's LossScaler with its state on the device: a 16-byte block [loss_scale f32, unskipped i32, overflows i32,
     last_overflow i32] that og_step_scale_amp_f32 reads and moves inside the optimizer's step (include/og_decoder.h has the rule).
@@ -61,10 +95,9 @@ class DeviceLossScaler:
         self.scale_factor, self.scale_window = float(scale_factor), int(scale_window)
         self.min_loss_scale, self.max_loss_scale = float(min_loss_scale), float(max_loss_scale)
         if device is None:
-            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+            device = 'cuda' if torch.cuda.is_available() else 'cpu'
+        device = torch.device(device)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device.type == 'cuda' and device.index is None else device
         # a tensor of its own, never a slice of the optimizer's workspace (that one is reallocated when the parameter list grows)
         self._block = self._words(start, 0, 0, 0).to(self.device)
 
@@ -142,10 +175,10 @@ class ModelEma:
         self.decay, self.warmup, self.updates = float(decay), bool(warmup), 0
         model = _unwrap(model)
         self.module = copy.deepcopy(model).eval().requires_grad_(False)
-        self._pool = _table.Pool()
-        self._signature = self._table = None
-        self._n_rows = self._n_chunks = self._prefix_at = 0
+        self._table = _DeviceTable()
         self.bind(model)
+
+    _n_rows = property(lambda self: self._table.n_rows)      # rows of the last update()'s launch
 
     def bind(self, model):
         """Pair the tensors of `model` (by state_dict() name) with the shadow's and bring every shadow tensor to its source's layout."""
@@ -162,7 +195,7 @@ class ModelEma:
                     e.data = torch.empty_like(x).copy_(e)
         self.tensors = {name: (x, shadow[name]) for name, x in source.items()}      # name -> (source tensor, shadow tensor)
         self._shadow_of = {x: e for x, e in self.tensors.values()}                   # tensors hash by identity
-        self._signature = None
+        self._table.forget()
 
     @torch.no_grad()
     def reset(self):
@@ -191,36 +224,28 @@ class ModelEma:
         """Queue one update of the average on the current stream, at decay_at(updates): ONE og_ema_lerp_f32 launch over every
         floating tensor of the shadow's state_dict() whose source is not in `skip` (the parameters an optimizer's fused update has
         just averaged), copy_ for the integer buffers (num_batches_tracked); updates += 1.  Never waits for the device."""
-        lib, dev = None, None
-        rows, counts, ints, seen = [], [], [], set()
+        dev = None
+        rows, ints, seen = [], [], set()
         for name, (x, e) in self.tensors.items():
             if e in seen:             # one tensor under two names (tied weights) is averaged once
                 continue
             seen.add(e)
             if not x.is_cuda or not e.is_cuda:
-                raise _lib.OgError(f'ModelEma.update: {name} on {x.device}; the HIP kernels need GPU tensors (offsetguided_amd has no '
-                                   'CPU path)')
+                raise _no_cpu_path('ModelEma.update', name, x)
             if not e.is_floating_point():
                 ints.append((e, x))
                 continue
             if x in skip or x.numel() == 0:
                 continue
-            if dev is None:
-                lib, dev = _lib.load(), x.device
-                chunk = lib.og_optim_chunk_elems()
+            dev = x.device if dev is None else dev
             _check_shadow(name, x, e, dev)
             rows.append((e.data_ptr(), x.data_ptr(), x.numel()))
-            counts.append(-(-x.numel() // chunk))
         omd = 1.0 - self.decay_at(self.updates)
         if rows:
+            lib, t = _lib.load(), self._table
             with torch.cuda.device(dev):
-                if rows != self._signature:
-                    raw, prefix, self._prefix_at = _table.pack(np.array(rows, dtype=np.int64).reshape(-1, 3), counts)
-                    self._table = _table.upload(raw, dev, self._pool)
-                    self._n_rows, self._n_chunks = len(rows), int(prefix[-1])
-                    self._signature = rows
-                at = self._table.data_ptr()
-                _lib.check(lib.og_ema_lerp_f32(at, at + self._prefix_at, self._n_rows, self._n_chunks, omd, _lib.stream_ptr(dev)), lib)
+                t.put(tuple(rows), rows, 3, lib.og_optim_chunk_elems(), dev)
+                _lib.check(lib.og_ema_lerp_f32(t.rows, t.prefix, t.n_rows, t.n_chunks, omd, _lib.stream_ptr(dev)), lib)
         for e, x in ints:
             e.copy_(x)
         self.updates += 1
@@ -249,20 +274,18 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._steps = {}          # parameter -> steps taken (the host's count; state[p]['step'] follows in state_dict())
         self._checked = set()     # parameters whose state tensors are known to have the parameter's layout
-        self._signature = None    # what the device table was built from
-        self._table = None
+        self._table = _DeviceTable()
         self._segments = []       # (group index, key, first chunk, chunk count)
-        self._n_rows = self._n_chunks = self._prefix_at = 0
-        self._pool = _table.Pool()
         self._ws = None
+
+    _n_chunks = property(lambda self: self._table.n_chunks)      # chunks of the last step's table
 
     # ---- the state block ------------------------------------------------------------------------------------------------------
     def _device(self):
         for group in self.param_groups:
             for p in group['params']:
                 if not p.is_cuda:
-                    raise _lib.OgError(f'{type(self).__name__}: parameter on {p.device}; the HIP optimizer kernels need GPU tensors '
-                                       '(offsetguided_amd has no CPU path)')
+                    raise _no_cpu_path(type(self).__name__, 'parameter', p)
                 return p.device
         raise _lib.OgError(f'{type(self).__name__}: no parameters')
 
@@ -277,20 +300,16 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             self._ws = ws
         return self._ws
 
-    @property
-    def last_grad_norm(self):
-        """fp32 device scalar: the gradient norm of the last step that computed one (before clipping)."""
-        return self._workspace(self._device(), _lib.load())[4:8].view(torch.float32)[0]
+    def _state_word(self, i, dtype):
+        """Word i of the workspace's state block [scale f32, norm f32, dropped i32] as a device scalar."""
+        return self._workspace(self._device(), _lib.load())[4 * i:4 * i + 4].view(dtype)[0]
 
-    @property
-    def last_scale(self):
-        """fp32 device scalar: what that step multiplied the gradients by (0: dropped, below 1: clipped)."""
-        return self._workspace(self._device(), _lib.load())[0:4].view(torch.float32)[0]
-
-    @property
-    def dropped_steps(self):
-        """int32 device scalar: steps dropped so far (loss above loss_limit, or a non-finite gradient)."""
-        return self._workspace(self._device(), _lib.load())[8:12].view(torch.int32)[0]
+    last_scale = property(lambda self: self._state_word(0, torch.float32),
+                          doc='fp32 device scalar: what the last step multiplied the gradients by (0: dropped, below 1: clipped).')
+    last_grad_norm = property(lambda self: self._state_word(1, torch.float32),
+                              doc='fp32 device scalar: the gradient norm of the last step that computed one (before clipping).')
+    dropped_steps = property(lambda self: self._state_word(2, torch.int32),
+                             doc='int32 device scalar: steps dropped so far (loss above loss_limit, or a non-finite gradient).')
 
     # ---- checkpoints ----------------------------------------------------------------------------------------------------------
     def state_dict(self):
@@ -311,7 +330,7 @@ class _DeviceOptimizer(torch.optim.Optimizer):
                 group.setdefault(k, v)
         self._steps = {p: int(round(float(st['step']))) for p, st in self.state.items() if st.get('step') is not None}
         self._checked = set()
-        self._signature = None
+        self._table.forget()
 
     # ---- the tensor table -----------------------------------------------------------------------------------------------------
     def _init_state(self, p, group, state):
@@ -320,8 +339,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
     def _key(self, p, group, state):
         raise NotImplementedError
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
-        """avg: None, or (address table, omd) of a step with a weight average."""
+    def _rule(self, group, key):
+        """(the entry point's stem, the rule's arguments) of the segment `key` of `group`: step() calls stem + '_f32' or '_ema_f32'."""
         raise NotImplementedError
 
     def _after(self, entries):
@@ -336,8 +355,7 @@ class _DeviceOptimizer(torch.optim.Optimizer):
                 if g is None:
                     continue
                 if not p.is_cuda or not g.is_cuda:
-                    raise _lib.OgError(f'{type(self).__name__}.step: parameter on {p.device}; the HIP optimizer kernels need GPU '
-                                       'tensors (offsetguided_amd has no CPU path)')
+                    raise _no_cpu_path(f'{type(self).__name__}.step', 'parameter', p)
                 if p.device != dev:
                     raise _lib.OgError(f'{type(self).__name__}.step: parameters on {dev} and {p.device}; one device per optimizer')
                 if p.dtype != torch.float32 or g.dtype != torch.float32 or g.is_sparse:
@@ -371,25 +389,19 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         return out
 
     def _upload(self, entries, dev, lib, ema=None):
-        chunk = lib.og_optim_chunk_elems()
         moments = self.MOMENTS + (None,) * (2 - len(self.MOMENTS))
         rows = [(p.data_ptr(), g.data_ptr(), *(st[k].data_ptr() if k and st.get(k) is not None else 0 for k in moments), p.numel())
                 for _, _, p, g, st in entries]
         keys = [e[:2] for e in entries]
         averages = None if ema is None else self._averages(entries, dev, ema)      # travels behind the rows, before the prefix
-        signature = (rows, keys) if ema is None else (rows, keys, averages)
-        if signature == self._signature:
+        prefix = self._table.put((rows, keys, averages), rows, 5, lib.og_optim_chunk_elems(), dev, averages)
+        if prefix is None:
             return
-        table = np.array(rows, dtype=np.int64).reshape(-1, 5)
-        raw, prefix, self._prefix_at = _table.pack(table, -(-table[:, 4] // chunk), averages)
         self._segments = []
         for i, key in enumerate(keys):
             if i == 0 or key != keys[i - 1]:
                 self._segments.append([key[0], key[1], int(prefix[i]), 0])
             self._segments[-1][3] = int(prefix[i + 1]) - self._segments[-1][2]
-        self._table = _table.upload(raw, dev, self._pool)
-        self._n_rows, self._n_chunks = len(rows), int(prefix[-1])
-        self._signature = signature
 
     @torch.no_grad()
     def step(self, closure=None, *, loss=None, max_grad_norm=math.inf, loss_limit=1e8, scaler=None, ema=None):
@@ -419,31 +431,28 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         with torch.cuda.device(dev):
             ws = self._workspace(dev, lib)
             self._upload(entries, dev, lib, ema)
-            stream = _lib.stream_ptr(dev)
-            rows, prefix = self._table.data_ptr(), self._table.data_ptr() + self._prefix_at
-            avg = None if ema is None else (rows + 40 * self._n_rows, 1.0 - ema.decay_at(ema.updates))
+            stream, t = _lib.stream_ptr(dev), self._table
+            suffix, avg = ('_f32', ()) if ema is None else ('_ema_f32', (t.extra, 1.0 - ema.decay_at(ema.updates)))
             state_ptr = None
             if loss is not None or math.isfinite(max_grad_norm) or scaler is not None:
                 if loss is not None:
                     loss = _lib.require_device(loss.detach(), 'loss')
                     if loss.numel() != 1:
                         raise ValueError(f'loss: one element expected, got {tuple(loss.shape)}')
-                _lib.check(lib.og_grad_sumsq_f32(rows, prefix, self._n_rows, self._n_chunks, _lib.ptr(ws), ws.numel(), stream), lib)
+                _lib.check(lib.og_grad_sumsq_f32(t.rows, t.prefix, t.n_rows, t.n_chunks, _lib.ptr(ws), ws.numel(), stream), lib)
                 loss_ptr = _lib.ptr(loss) if loss is not None else None
                 if scaler is None:
-                    _lib.check(lib.og_step_scale_f32(self._n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(ws), ws.numel(),
+                    _lib.check(lib.og_step_scale_f32(t.n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(ws), ws.numel(),
                                                      stream), lib)
                 else:
-                    _lib.check(lib.og_step_scale_amp_f32(self._n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(scaler._block),
+                    _lib.check(lib.og_step_scale_amp_f32(t.n_chunks, loss_ptr, loss_limit, max_grad_norm, _lib.ptr(scaler._block),
                                                          int(scaler.dynamic), scaler.scale_factor, scaler.scale_window,
                                                          scaler.min_loss_scale, scaler.max_loss_scale, _lib.ptr(ws), ws.numel(),
                                                          stream), lib)
                 state_ptr = _lib.ptr(ws)
             for gi, key, first, count in self._segments:
-                if avg is None:
-                    self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream)
-                else:
-                    self._launch(lib, self.param_groups[gi], key, rows, prefix, first, count, state_ptr, stream, avg)
+                stem, args = self._rule(self.param_groups[gi], key)
+                _lib.check(getattr(lib, stem + suffix)(t.rows, t.prefix, t.n_rows, first, count, state_ptr, *args, *avg, stream), lib)
             if ema is not None:
                 ema.update(skip={p for _, _, p, _, _ in entries if ema.shadow_of(p) is not None})
         self._after(entries)
@@ -470,17 +479,11 @@ class DeviceAdam(_DeviceOptimizer):
     def _key(self, p, group, state):
         return self._steps[p]
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
+    def _rule(self, group, key):
         t = key + 1
         b1, b2 = group['betas']
-        if avg is not None:
-            _lib.check(lib.og_adam_step_ema_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], b1, b2, 1.0 - b1,
-                                                1.0 - b2, group['eps'], group['weight_decay'], 1.0 - b1 ** t, 1.0 - b2 ** t,
-                                                int(group.get('adam_w_mode', True)), *avg, stream), lib)
-            return
-        _lib.check(lib.og_adam_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], b1, b2, 1.0 - b1, 1.0 - b2,
-                                        group['eps'], group['weight_decay'], 1.0 - b1 ** t, 1.0 - b2 ** t,
-                                        int(group.get('adam_w_mode', True)), stream), lib)
+        return 'og_adam_step', (group['lr'], b1, b2, 1.0 - b1, 1.0 - b2, group['eps'], group['weight_decay'], 1.0 - b1 ** t,
+                                1.0 - b2 ** t, int(group.get('adam_w_mode', True)))
 
     def _after(self, entries):
         for _, _, p, _, _ in entries:
@@ -509,13 +512,8 @@ class DeviceSGD(_DeviceOptimizer):
     def _key(self, p, group, state):
         return 1 if p in self._fresh else 0
 
-    def _launch(self, lib, group, key, rows, prefix, first, count, state_ptr, stream, avg=None):
-        if avg is not None:
-            _lib.check(lib.og_sgd_step_ema_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], group['momentum'],
-                                               group['weight_decay'], key, *avg, stream), lib)
-            return
-        _lib.check(lib.og_sgd_step_f32(rows, prefix, self._n_rows, first, count, state_ptr, group['lr'], group['momentum'],
-                                       group['weight_decay'], key, stream), lib)
+    def _rule(self, group, key):
+        return 'og_sgd_step', (group['lr'], group['momentum'], group['weight_decay'], key)
 
     def _after(self, entries):
         self._fresh.difference_update(e[2] for e in entries)
